@@ -1,6 +1,15 @@
 """Benchmark of the MI355X ASW stereo hot path (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c1|c2|c3|c5] [--api stage|frame]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--full``
+adds what takes runs of its own: ``cpu_baseline``, the den-none passes beside the
+shipped den-read ones (``roofline.v_none_ms`` / ``h_none_ms``) and, on N > 1,
+``frame_groups``; without it those fields are null or absent.  ``--dump-outputs DIR``
+writes what the last timed step returned (the MatchResult fields; the frame API's and the
+refinement's arrays) as DIR/<name>.npy in float32, a seeded sample of the arrays too
+large for the 60 MB it writes in all; the inputs are the same from run to run.
 
 One step = one disparity map per frame group (C5: a batch of 8 pairs): raw cost
 -> 4 support launches -> r x (V, H) aggregation passes -> WTA (+ target map) ->
@@ -17,7 +26,7 @@ N ranks with RCCL MIN all-reduces for the WTA (BASELINE.json config 4: "d-axis
 sharded across 8x MI355X via RCCL"; at N = 8 each rank owns 32 of the 256 planes
 and runs the half-wave passes of asw_pass32.h): "scaling": "strong", the frame's
 total work is fixed.  ``--group-size G`` splits the N ranks into N/G concurrent
-frames of G shards instead; without it, the layout with the most maps/s,
+frames of G shards instead; without it, with ``--full``, the layout with the most maps/s,
 plan_groups(D, N) ranks per frame, is timed after the main run and reported beside
 ``value`` as ``frame_groups`` (not as ``value``).  On N > 1 the frames are streamed
 (``--pipeline``, default on there): frame k's WTA tail — the four RCCL all-reduces with
@@ -36,7 +45,7 @@ n local cost planes, read both support arrays of the direction) ove
 the launch's average duration from HIP events recorded on the stream the passes
 run on, inside the timed region.  ``traffic`` = that kernel's HBM bytes per
 launch from rocprofv3 PMC (profiles/traffic.json, tools/traffic_json.py).
-``cpu_baseline`` is the CPU oracle (oracle/, a scalar-semantics C/OpenMP
+``cpu_baseline`` (``--full``) is the CPU oracle (oracle/, a scalar-semantics C/OpenMP
 restatement of the reference kernels) on this host: a full frame with every
 OpenMP thread (C5: a strip), and a 1-thread strip (median of 3).
 """
@@ -55,6 +64,8 @@ sys.path.insert(0, HERE)
 
 METRIC = "disparity maps/sec + ms/frame, 1920×1080 d=256 ASW win=35, 1/2/4/8 MI355X"
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s (spec)
+DUMP_BUDGET = 60 << 20  # bytes of array data --dump-outputs writes, all files together
+DUMP_MIN = 1 << 20  # elements of every array it writes at least (the whole of a smaller one)
 
 WORKLOADS = {
     # name: (W, H, D, T, iters, lr, description)
@@ -74,7 +85,7 @@ REFINE = {k: 6 for k in WORKLOADS if k.startswith("ref-")}  # refinement iterati
 BATCH = {"c5": 8}  # pairs per step
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -86,7 +97,14 @@ def parse():
                     help="stage: device-resident StereoMatcher; frame: the C-ABI asw_match (host buffers)")
     ap.add_argument("--graph", action="store_true",
                     help="with --api frame: asw_set_graph (the device work replayed from HIP graphs)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure, everything that takes runs of its own: the CPU oracle "
+                         "baseline (cpu_baseline), the den-none passes timed after the timed region "
+                         "(roofline v/h_none), and on N > 1 the plan_groups layout (frame_groups)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         f"(float32; at most {DUMP_BUDGET >> 20} MB in all, a seeded sample of a larger array)")
     ap.add_argument("--pipeline", default="auto", choices=["auto", "on", "off"],
                     help="stream the frames through two sets of volumes: frame k's WTA tail (the RCCL exchange, "
                          "target scan, LR check) on a side stream overlapping frame k+1's aggregation "
@@ -102,7 +120,7 @@ def parse():
     ap.add_argument("--group-size", type=int, default=0,
                     help="ranks per d-sharded frame (0: one frame over all ranks; the plan_groups layout is timed "
                          "beside it as frame_groups)")
-    return ap.parse_args()
+    return ap.parse_args(argv)
 
 
 def cpu_model() -> str:
@@ -254,6 +272,51 @@ def load_pairs(workload, W, H, D, n):
     return out
 
 
+def named_arrays(obj, prefix=""):
+    """Every array of a step's return value (a MatchResult, the frame API's or refine()'s dict,
+    a list of them over the batch) by name: {"d_ref": ..., "refine_final_rgba": ..., "pair1_d_ref": ...}."""
+    import dataclasses
+
+    import torch
+    if dataclasses.is_dataclass(obj):
+        obj = {f.name: getattr(obj, f.name) for f in dataclasses.fields(obj)}
+    if isinstance(obj, (torch.Tensor, np.ndarray)):
+        return {prefix.rstrip("_"): obj}
+    out = {}
+    if isinstance(obj, dict):
+        for k, v in obj.items():
+            out.update(named_arrays(v, f"{prefix}{k}_" if k else prefix))
+    return out
+
+
+def dump_outputs(dirname, arrays):
+    """DIR/<name>.npy, float32 (the integer maps and 8-bit images are exact in it), DUMP_BUDGET
+    bytes in all.  Every array is sure of DUMP_MIN elements; what is left goes to the smallest
+    arrays first, whole where it suffices (C4: the six maps whole, the two LR images and the
+    cost volume sampled).  A sample is the array at fixed (seed 0) sorted flat indices, taken
+    on the array's own device."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    size = lambda a: a.numel() if isinstance(a, torch.Tensor) else a.size  # noqa: E731
+    todo = sorted(arrays.items(), key=lambda kv: (size(kv[1]), kv[0]))
+    sure = min(DUMP_MIN, DUMP_BUDGET // 4 // max(len(todo), 1))
+    left = DUMP_BUDGET // 4 - sum(min(size(a), sure) for _, a in todo)  # float32 elements
+    rng = np.random.default_rng(0)
+    for i, (name, a) in enumerate(todo):
+        n = size(a)
+        more = max(n - sure, 0)
+        if more > left:
+            more = left // (len(todo) - i)
+        take = min(n, sure) + more
+        left -= more
+        if take < n:
+            idx = np.sort(rng.integers(0, n, take))
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device) if isinstance(a, torch.Tensor) else idx]
+        if isinstance(a, torch.Tensor):
+            a = a.cpu().numpy()
+        np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     args = parse()
     import torch
@@ -329,21 +392,26 @@ def main():
         fc = FrameContext(p, devices=[local], refine=_lib.default_refine_params(iters=k_ref), graph=args.graph)
 
     def step(events=None):
+        """One step; returns what its calls returned, per pair of the batch (--dump-outputs)."""
+        outs = []
         for b in range(batch):
             if frame:
                 out = fc.match(*pairs_h[b])
                 spans.append(out["timings"])
+                outs.append(out)
             else:
                 ev = [] if events is not None else None
                 res = m.submit(*pairs[b], events=ev) if args.pipeline else m.match(*pairs[b], events=ev)
+                outs.append(res)
                 if k_ref:  # main.cpp:540-623: k x (ref_v, ref_h, WTA_REF, LR) + 3x3 median
                     from stereo_matchin_amd import _lib
-                    m.refine(res, *pairs[b], rp=_lib.default_refine_params(iters=k_ref))
+                    outs[-1] = {"": res, "refine": m.refine(res, *pairs[b], rp=_lib.default_refine_params(iters=k_ref))}
                     if ev is not None:
                         from stereo_matchin_amd.pipeline import _record
                         ev.append(("refine", _record()))
                 if events is not None:
                     events.append(ev)
+        return outs
 
     for _ in range(args.warmup):
         step()
@@ -357,8 +425,9 @@ def main():
 
     evs = []
     t0 = time.perf_counter()
+    last = []
     for _ in range(args.steps):
-        step(evs)
+        last = step(evs)
     if args.pipeline:
         m.flush()
     torch.cuda.synchronize()
@@ -366,6 +435,12 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0:
+        # now: the --full runs below reuse the matcher's volumes (MatchResult.cost is one of them)
+        arrays = {}
+        for b, o in enumerate(last):
+            arrays.update(named_arrays(o, f"pair{b}_" if batch > 1 else ""))
+        dump_outputs(args.dump_outputs, arrays)
 
     # the instantiations the timed frames ran, per (direction, den mode), queried now:
     # the frame_groups run below launches other ones
@@ -409,7 +484,7 @@ def main():
     # the faster): one V and one H pass without the cached denominators, on the
     # matcher's own buffers, after the timed region (not part of `value`)
     v_none, h_none = [], []
-    if not frame and not args.pipeline and world == 1 and iters >= 2:
+    if args.full and not frame and not args.pipeline and world == 1 and iters >= 2:
         from stereo_matchin_amd import kernels as K
         for _ in range(3):
             e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
@@ -424,7 +499,7 @@ def main():
     # the layout with the most maps/s (plan_groups: N/g concurrent frames of g shards),
     # timed after the main run and reported beside `value`
     frame_groups = None
-    g2 = plan_groups(D, world) if world > 1 and not args.group_size and not frame else 1
+    g2 = plan_groups(D, world) if args.full and world > 1 and not args.group_size and not frame else 1
     if 1 < g2 < world:
         subs2 = [dist.new_group(list(range(g * g2, (g + 1) * g2)), backend="gloo" if rehearsal else None)
                  for g in range(world // g2)]
@@ -535,7 +610,7 @@ def main():
                                        if in_frame_none else
                                        "the frame ships cached denominators (den-read) for r >= 2: den-none "
                                        "(v/h_none, 3 VALU per voxel-tap instead of 2, 2.1 GB less traffic) is "
-                                       "timed beside it outside the timed region"),
+                                       "timed beside it outside the timed region with --full"),
                          "all_pass_mean_ms": round(pass_avg, 4),
                          "all_pass_frac": round(gbs(pass_avg) / HBM_PEAK_GBS, 4),
                          "timing": "frame API: asw_timings per-direction means over all r passes" if frame else
@@ -553,7 +628,7 @@ def main():
             out["pcie_inclusive"] = {"value": round(n_maps / elapsed, 4), "unit": "maps/s",
                                      "note": "wall clock of asw_match incl. host->device upload and device->host "
                                              "read-back of every output"}
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             rows = args.cpu_rows or (96 if args.workload == "c5" else H)
             out["cpu_baseline"] = cpu_baseline(*pairs_h[0], D, T, iters, rows, lr_mode)
         else:

@@ -4,8 +4,8 @@
 # steps:
 #   test        pytest -m gpu (whole suite)           test:EXPR  only tests matching -k EXPR
 #   smoke       __graft_entry__.smoke()
-#   bench       python bench.py (default workload, with cpu_baseline)
-#   bench:ARGS  python bench.py ARGS  ('+'-separated, e.g. bench:--workload+c5+--steps+3)
+#   bench       python bench.py --full (default workload, with cpu_baseline, den-none passes, frame_groups)
+#   bench:ARGS  python bench.py --full ARGS  ('+'-separated, e.g. bench:--workload+c5+--steps+3)
 #   prof        rocprofv3 --kernel-trace --stats of bench.py --no-cpu
 #   prof:ARGS   the same with bench.py ARGS
 #   profpy:ARGS rocprofv3 --kernel-trace --stats of python3 ARGS (a tool script)
@@ -61,7 +61,7 @@ for step in "$@"; do
                 run 1100 "pytest_$TAG" $PY -m pytest tests -m gpu -x -q --timeout 240 --timeout-method thread
             fi ;;
         smoke) run 300 "smoke_$TAG" $PY -c "import __graft_entry__ as g; g.smoke()" ;;
-        bench) run 600 "bench_$TAG${arg:+_${args// /_}}" $PY bench.py $args ;;
+        bench) run 600 "bench_$TAG${arg:+_${args// /_}}" $PY bench.py --full $args ;;
         prof)
             run 600 "prof_$TAG" rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
                 python3 bench.py --steps 5 --warmup 1 --no-cpu $args ;;

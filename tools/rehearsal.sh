@@ -6,6 +6,6 @@ set -e
 O=$1; N=$2; shift 2
 mkdir -p "$O"
 ASW_BENCH_REHEARSAL=1 timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" \
-    --master-addr 127.0.0.1 --master-port $((29400 + RANDOM % 500)) bench.py --gpus "$N" --steps 2 --warmup 1 --no-cpu "$@" \
+    --master-addr 127.0.0.1 --master-port $((29400 + RANDOM % 500)) bench.py --gpus "$N" --steps 2 --warmup 1 --full --no-cpu "$@" \
     > "$O/rehearsal$N${1:+_g}.log" 2>&1
 grep '^{' "$O/rehearsal$N${1:+_g}.log"
