@@ -90,7 +90,11 @@ int asw_last_hip_error(void); /* hipError_t of the last ASW_E_HIP */
  *   3: asw_params.flags (the context options that were environment variables);
  *      asw_raw_cost16 / asw_aggregate_pass_den16 (the uint16 raw-cost volume);
  *   4: the measured-negative forms removed with their entry points and flags
- *      (on-the-fly, index-form and fused-raw passes, the fused WTA scan). */
+ *      (on-the-fly, index-form and fused-raw passes, the fused WTA scan).
+ * Additive within revision 4 (no struct above changes its layout, no flag is added):
+ *      the sub-pixel entry points asw_subpixel / asw_subpixel_local /
+ *      asw_subpixel_finalize / asw_disp_mask / asw_disp_fill and asw_set_subpixel with
+ *      its own asw_subpixel_outputs struct. */
 #define ASW_ABI_VERSION 4
 int asw_abi_version(void);
 
@@ -204,6 +208,35 @@ int asw_wta_second(const asw_params *p, const int64_t *key_global, const int64_t
 int asw_wta_finalize(const asw_params *p, const int64_t *key, const float *m2, const int64_t *tkey,
                      const float *t2, int32_t *d_ref, float *conf_ref, int32_t *d_tar, float *conf_tar,
                      uint8_t *code_ref, uint8_t *code_tar, void *stream);
+
+/* ---- sub-pixel float disparity maps (no reference counterpart: the reference writes
+ * 8-bit codes only).  Every operation is an IEEE float32 one, in this order
+ * (DESIGN.md §Sub-pixel).  With d = d_ref[p] (the first argmin) and c0 = C[p][d],
+ * cm = C[p][d-1], cp = C[p][d+1] of the final aggregated volume:
+ *   d == 0 or d == ndisp-1:  disp[p] = (float)d
+ *   else  a = cm - c0;  b = cp - c0;  disp[p] = (float)d + (a - b) / (2.0f * (a + b))
+ * (the quotient correctly rounded; a > 0, b >= 0, so the offset lies in (-0.5, 0.5]).
+ * Planes >= ndisp (pitch padding) are never read.
+ *   asw_subpixel: whole-volume p only (d_begin = 0, d_end = ndisp), else ASW_E_INVALID.
+ * d-sharded (after the first MIN all-reduce of the asw_wta_local protocol):
+ *   asw_subpixel_local(key_global) -> allreduce_min(nb) -> asw_subpixel_finalize.
+ * nb is [3][S] float32: nb[j][p] = C[p][d-1+j] where this shard owns plane d-1+j (and it
+ * lies in [0, ndisp)), +INF elsewhere; d = low 32 bits of key_global[p].  The three
+ * floats that survive the MIN are the ones asw_subpixel reads: bit-identical. */
+int asw_subpixel(const asw_params *p, const float *cost, const int32_t *d_ref, float *disp, void *stream);
+int asw_subpixel_local(const asw_params *p, const float *cost, const int64_t *key_global, float *nb, void *stream);
+int asw_subpixel_finalize(const asw_params *p, const int64_t *key_global, const float *nb, float *disp,
+                          void *stream);
+/* disp_lr[p] = disp[p] where the LR rule of asw_outputs.lr16 passes (ASW_LR_U8: the 8-bit
+ * codes of K/consist.cl:20-30; ASW_LR_NATIVE: |d_ref - d_tar| <= 1), else a quiet NaN.
+ * code_ref / code_tar may be NULL with ASW_LR_NATIVE. */
+int asw_disp_mask(const asw_params *p, const float *disp, const int32_t *d_ref, const int32_t *d_tar,
+                  const uint8_t *code_ref, const uint8_t *code_tar, float *disp_lr, void *stream);
+/* background fill per row: a valid (non-NaN) pixel is copied; an invalid one takes the
+ * smaller of its nearest valid neighbours to the left and to the right in its row (the
+ * one that exists at a row end, 0.0f in a row without a valid pixel).  The output holds
+ * no NaN.  disp_lr != disp_filled. */
+int asw_disp_fill(const asw_params *p, const float *disp_lr, float *disp_filled, void *stream);
 
 /* ---- d-sharded asw_WTA_REF (K/asw_wta_ref.cl:2-68): the refinement loop's volume
  * scan over a shard, the asw_wta_local protocol on the penalised values
@@ -378,6 +411,24 @@ int asw_set_refine(asw_ctx *ctx, const asw_refine_params *rp);
  * the loop) kernel launches, for small, launch-bound frames.  Same results.  Only
  * the coarse timings (h2d, total, refine, d2h) are measured.  One-shard contexts. */
 int asw_set_graph(asw_ctx *ctx, int on);
+/* Sub-pixel float maps of the left view (asw_subpixel, asw_disp_mask, asw_disp_fill):
+ * caller-owned host [H][W] float32 arrays, any may be NULL.  asw_set_subpixel copies
+ * the struct and allocates the device maps once; every later asw_match fills the
+ * registered arrays (asw_match_batch: pair b at offset b*H*W of each).  o = NULL: off
+ * (the default; a frame then launches nothing new).  disp_lr / disp_filled need
+ * lr_check (ASW_E_INVALID without).  The maps are pre-refinement results like every
+ * other map.  A multi-shard context runs the asw_subpixel_local protocol: one more MIN
+ * all-reduce ([3][S] float32), maps on the first shard, bit-identical to one GPU (with
+ * asw_create_rank every rank must turn the maps on or off alike: the all-reduce is
+ * collective; every rank then receives the maps).  With
+ * asw_set_graph on the kernels run on the stream after the graph replay (not captured).
+ * Their time is inside asw_timings.total and in no stage column. */
+typedef struct asw_subpixel_outputs {
+    float *disp;        /* d_ref + parabola offset                                  */
+    float *disp_lr;     /* disp where the LR check passes, else NaN                 */
+    float *disp_filled; /* disp_lr with the holes filled from the row's background  */
+} asw_subpixel_outputs;
+int asw_set_subpixel(asw_ctx *ctx, const asw_subpixel_outputs *o);
 
 #ifdef __cplusplus
 }

@@ -7,12 +7,12 @@ reference's kernel interface (:mod:`.kernels`), the one-GPU pipeline
 (:mod:`.pipeline`) and disparity-axis sharding over RCCL (:mod:`.distributed`).
 """
 from ._lib import (ASW_OK, COLOR_LAB, COLOR_RGB, DIR_H, DIR_V, LR_NATIVE, LR_U8, AswError,  # noqa: F401
-                   AswLibraryError, AswParams, default_params)
+                   AswLibraryError, AswParams, AswSubpixelOutputs, default_params)
 from .pipeline import (FrameContext, MatchResult, StereoMatcher, comm_unique_id, make_params,  # noqa: F401
                        match_frame, to_rgba)
 
 __all__ = [
     "AswParams", "AswError", "AswLibraryError", "StereoMatcher", "MatchResult", "make_params", "match_frame",
     "FrameContext", "comm_unique_id",
-    "to_rgba", "default_params",
+    "to_rgba", "default_params", "AswSubpixelOutputs",
 ]

@@ -97,6 +97,12 @@ class AswOutputs(ctypes.Structure):
     ]
 
 
+class AswSubpixelOutputs(ctypes.Structure):
+    """Mirror of ``asw_subpixel_outputs`` (include/asw.h): host float32 [H][W] arrays."""
+
+    _fields_ = [("disp", ctypes.c_void_p), ("disp_lr", ctypes.c_void_p), ("disp_filled", ctypes.c_void_p)]
+
+
 class AswRefineParams(ctypes.Structure):
     """Mirror of ``asw_refine_params`` (include/asw.h)."""
 
@@ -165,6 +171,12 @@ SIGNATURES = {
     "asw_refine": (I, [PP, RP, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "asw_set_refine": (I, [P, RP]),
     "asw_set_graph": (I, [P, I]),
+    "asw_subpixel": (I, [PP, P, P, P, P]),
+    "asw_subpixel_local": (I, [PP, P, P, P, P]),
+    "asw_subpixel_finalize": (I, [PP, P, P, P, P]),
+    "asw_disp_mask": (I, [PP, P, P, P, P, P, P, P]),
+    "asw_disp_fill": (I, [PP, P, P, P]),
+    "asw_set_subpixel": (I, [P, P]),
     "asw_tune_set": (I, [I, I]),
     "asw_pass_kernel": (I, [I, I, ctypes.c_char_p, I]),
     "asw_device_name": (I, [I, ctypes.c_char_p, I]),

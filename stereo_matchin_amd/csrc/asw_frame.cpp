@@ -46,6 +46,7 @@ struct Shard {
     ncclComm_t comm = nullptr;
     hipEvent_t ready = nullptr;  // COMM_LOCAL: this shard's operand is complete
     float *ref_l = nullptr, *ref_r = nullptr;  // sharded refinement, shards > 0: the per-view estimates
+    float *nb = nullptr;  // asw_set_subpixel on a sharded frame: [3][S] neighbour costs of the winner
 };
 
 }  // namespace
@@ -75,6 +76,10 @@ struct asw_ctx {
     bool graph = false;
     hipGraph_t g_main = nullptr, g_ref = nullptr;
     hipGraphExec_t gx_main = nullptr, gx_ref = nullptr;
+    // asw_set_subpixel: the registered host arrays and their device maps (shard 0's device)
+    asw_subpixel_outputs sub{};
+    bool sub_on = false;
+    float *sp_disp = nullptr, *sp_lr = nullptr, *sp_fill = nullptr;
 };
 
 namespace {
@@ -167,10 +172,11 @@ __global__ void k_min_n(long long count, MinOperands ops, T *out) {
 size_t frame_pixels(const asw_params *p) { return (size_t)p->width * p->height; }
 
 // In-place elementwise MIN all-reduce of buf(shard) (count elements of T) over
-// every shard of the frame.  Stream-ordered on each shard's stream.
+// every shard of the frame.  Stream-ordered on each shard's stream
+// (`per_pixel` elements per pixel: 1 for the WTA's maps, 3 for the sub-pixel neighbours).
 template <class T>
-int allreduce_min(asw_ctx *c, T *(*buf)(Shard &), ncclDataType_t type) {
-    const size_t S = frame_pixels(&c->p);
+int allreduce_min(asw_ctx *c, T *(*buf)(Shard &), ncclDataType_t type, int per_pixel = 1) {
+    const size_t S = frame_pixels(&c->p) * (size_t)per_pixel;
     if (c->comm == COMM_RCCL) {
         NCCLCHK(ncclGroupStart());
         for (int i = 0; i < c->n; ++i) {
@@ -229,13 +235,14 @@ int64_t *b_key_g(Shard &s) { return s.key_g; }
 int64_t *b_tkey_g(Shard &s) { return s.tkey_g; }
 float *b_m2_g(Shard &s) { return s.m2_g; }
 float *b_t2_g(Shard &s) { return s.t2_g; }
+float *b_nb(Shard &s) { return s.nb; }
 
 void free_shard(Shard &s) {
     if (s.stream == nullptr && s.left == nullptr) return;
     (void)hipSetDevice(s.device);
     void *bufs[] = {s.left, s.right, s.lut, s.lab_l, s.lab_r, s.wvl, s.wvr, s.whl, s.whr, s.c0, s.c1, s.den_v,
                     s.den_h, s.key, s.key_g, s.tkey, s.tkey_g, s.m1, s.m2, s.t1, s.t2, s.m2_g, s.t2_g, s.ref_l,
-                    s.ref_r};
+                    s.ref_r, s.nb};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (s.comm) (void)ncclCommDestroy(s.comm);
@@ -301,7 +308,8 @@ int destroy_ctx(asw_ctx *c) {
     for (int i = 0; i < kMaxShards; ++i) free_shard(c->sh[i]);
     (void)hipSetDevice(c->sh[0].device);
     void *bufs[] = {c->red_tmp, c->d_ref, c->d_tar, c->conf_ref, c->conf_tar, c->code_ref, c->code_tar, c->lr,
-                    c->lr_red, c->disp, c->disp16, c->lr16, c->rws, c->est, c->post_red, c->final_rgba};
+                    c->lr_red, c->disp, c->disp16, c->lr16, c->rws, c->est, c->post_red, c->final_rgba,
+                    c->sp_disp, c->sp_lr, c->sp_fill};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (hipEvent_t e : c->ev)
@@ -389,8 +397,8 @@ int create_ctx(const asw_params *p, const int *devs, int n, int shard0, int tota
         chain(dev_alloc(&c->disp, S * 4));
         chain(dev_alloc(&c->disp16, S * 2));
         chain(dev_alloc(&c->lr16, S * 2));
-        // h2d, raw, support, 2r+1 pass marks, exchange, wta, consistency, refine, d2h
-        c->ev.assign(2 * (size_t)p->iters + 10, nullptr);
+        // h2d, raw, support, 2r+1 pass marks, exchange, wta, consistency, refine, d2h, sub-pixel start
+        c->ev.assign(2 * (size_t)p->iters + 11, nullptr);
         for (hipEvent_t &e : c->ev)
             if (s == ASW_OK) chain(hipEventCreate(&e) == hipSuccess ? ASW_OK : ASW_E_HIP);
     }
@@ -585,6 +593,33 @@ int refine_work(asw_ctx *c) {
     return refine_sharded(c);
 }
 
+// The sub-pixel maps (asw_set_subpixel) from the frame's WTA results, on shard 0's
+// stream after the consistency stage and before the refinement loop touches anything.
+// One shard: asw_subpixel on the volume.  Sharded: every shard offers the neighbour
+// planes it owns of the global winner (key_g, still the first all-reduce's result), one
+// MIN all-reduce of the [3][S] array, finalize on shard 0 from the same three floats.
+int subpixel_work(asw_ctx *c) {
+    const asw_params *p = &c->p;
+    Shard &s0 = c->sh[0];
+    hipStream_t st = s0.stream;
+    if (c->comm == COMM_NONE) {
+        ASWCHK(asw_subpixel(&s0.p, s0.c0, c->d_ref, c->sp_disp, st));
+    } else {
+        for (int i = 0; i < c->n; ++i) {
+            Shard &s = c->sh[i];
+            HIPCHK(hipSetDevice(s.device));
+            ASWCHK(asw_subpixel_local(&s.p, s.c0, s.key_g, s.nb, s.stream));
+        }
+        ASWCHK(allreduce_min<float>(c, b_nb, ncclFloat32, 3));
+        HIPCHK(hipSetDevice(s0.device));
+        ASWCHK(asw_subpixel_finalize(p, s0.key_g, s0.nb, c->sp_disp, st));
+    }
+    if (c->sp_lr)
+        ASWCHK(asw_disp_mask(p, c->sp_disp, c->d_ref, c->d_tar, c->code_ref, c->code_tar, c->sp_lr, st));
+    if (c->sp_fill) ASWCHK(asw_disp_fill(p, c->sp_lr, c->sp_fill, st));
+    return ASW_OK;
+}
+
 // capture fn's work on stream st into *g / *gx (once), then launch it
 template <class F>
 int graph_run(hipStream_t st, hipGraph_t *g, hipGraphExec_t *gx, F &&fn) {
@@ -609,7 +644,8 @@ int graph_run(hipStream_t st, hipGraph_t *g, hipGraphExec_t *gx, F &&fn) {
     return ASW_OK;
 }
 
-int match_one(asw_ctx *c, const uint8_t *left_rgba, const uint8_t *right_rgba, asw_outputs *o, asw_timings *t) {
+int match_one(asw_ctx *c, const uint8_t *left_rgba, const uint8_t *right_rgba, asw_outputs *o, asw_timings *t,
+              size_t pair = 0) {
     const asw_params *p = &c->p;
     const size_t S = frame_pixels(p);
     const int r = p->iters;
@@ -617,9 +653,10 @@ int match_one(asw_ctx *c, const uint8_t *left_rgba, const uint8_t *right_rgba, a
     hipStream_t st = s0.stream;
     std::vector<hipEvent_t> &ev = c->ev;
     // event slots: 0 h2d start, 1 h2d end = raw start, 2 raw end, 3.. 3+2r pass marks,
-    // then exchange end, wta end, consistency end, pre-refinement d2h end, refine end, d2h end
+    // then exchange end, wta end, consistency end (= end of `total`), pre-refinement d2h end,
+    // refine end, d2h end; sub-pixel maps on: their start (they end at "consistency end")
     const int e_pass0 = 3, e_x = e_pass0 + 2 * r + 1, e_wta = e_x + 1, e_cons = e_x + 2, e_pre = e_x + 3,
-              e_ref = e_x + 4, e_d2h = e_x + 5;
+              e_ref = e_x + 4, e_d2h = e_x + 5, e_sub = e_x + 6;
     const bool graphed = c->graph && c->comm == COMM_NONE;
     HIPCHK(hipSetDevice(s0.device));
     HIPCHK(hipEventRecord(ev[0], st));
@@ -654,8 +691,19 @@ int match_one(asw_ctx *c, const uint8_t *left_rgba, const uint8_t *right_rgba, a
             HIPCHK(hipGetLastError());
         }
     }
+    if (c->sub_on) {  // never captured: launched on the stream after the graph replay
+        HIPCHK(hipEventRecord(ev[e_sub], st));
+        ASWCHK(subpixel_work(c));
+    }
     HIPCHK(hipEventRecord(ev[e_cons], st));
     // pre-refinement outputs leave before the loop updates its buffers in place
+    if (c->sub_on) {
+        const size_t off = pair * S;
+        if (c->sub.disp) HIPCHK(hipMemcpyAsync(c->sub.disp + off, c->sp_disp, S * 4, hipMemcpyDeviceToHost, st));
+        if (c->sub.disp_lr) HIPCHK(hipMemcpyAsync(c->sub.disp_lr + off, c->sp_lr, S * 4, hipMemcpyDeviceToHost, st));
+        if (c->sub.disp_filled)
+            HIPCHK(hipMemcpyAsync(c->sub.disp_filled + off, c->sp_fill, S * 4, hipMemcpyDeviceToHost, st));
+    }
     if (o) {
         if (o->d_ref) HIPCHK(hipMemcpyAsync(o->d_ref, c->d_ref, S * 4, hipMemcpyDeviceToHost, st));
         if (o->d_tar) HIPCHK(hipMemcpyAsync(o->d_tar, c->d_tar, S * 4, hipMemcpyDeviceToHost, st));
@@ -722,7 +770,7 @@ int match_one(asw_ctx *c, const uint8_t *left_rgba, const uint8_t *right_rgba, a
         const bool sharded = c->comm != COMM_NONE;
         t->exchange = sharded ? ms_between(ev[e_pass0 + 2 * r], ev[e_x]) : 0.0;
         t->wta = sharded ? t->exchange : ms_between(ev[e_x], ev[e_wta]);
-        t->consistency = ms_between(ev[e_wta], ev[e_cons]);
+        t->consistency = ms_between(ev[e_wta], ev[c->sub_on ? e_sub : e_cons]);  // the sub-pixel maps: in no column
         t->total = ms_between(ev[1], ev[e_cons]);
         t->refine = refine ? ms_between(ev[e_pre], ev[e_ref]) : 0.0;
         t->d2h = ms_between(ev[e_cons], ev[e_pre]) + ms_between(ev[e_ref], ev[e_d2h]);
@@ -829,6 +877,36 @@ int asw_set_refine(asw_ctx *c, const asw_refine_params *rp) {
     return ASW_OK;
 }
 
+int asw_set_subpixel(asw_ctx *c, const asw_subpixel_outputs *o) {
+    if (!c) return ASW_E_INVALID;
+    if (!o || (!o->disp && !o->disp_lr && !o->disp_filled)) {
+        c->sub_on = false;
+        c->sub = asw_subpixel_outputs{};
+        return ASW_OK;
+    }
+    if ((o->disp_lr || o->disp_filled) && !c->p.lr_check) return ASW_E_INVALID;  // they are LR-masked maps
+    const size_t S = frame_pixels(&c->p);
+    if (c->comm != COMM_NONE) {
+        for (int i = 0; i < c->n; ++i) {
+            Shard &s = c->sh[i];
+            HIPCHK(hipSetDevice(s.device));
+            if (!s.nb) ASWCHK(dev_alloc(&s.nb, 3 * S * 4));
+        }
+    }
+    HIPCHK(hipSetDevice(c->sh[0].device));
+    if (c->red_tmp && !c->sp_disp) {  // peer operands of the device-local exchange: 12 bytes per pixel now
+        (void)hipFree(c->red_tmp);
+        c->red_tmp = nullptr;
+        ASWCHK(dev_alloc(&c->red_tmp, (size_t)(c->n - 1) * S * 12));
+    }
+    if (!c->sp_disp) ASWCHK(dev_alloc(&c->sp_disp, S * 4));
+    if ((o->disp_lr || o->disp_filled) && !c->sp_lr) ASWCHK(dev_alloc(&c->sp_lr, S * 4));
+    if (o->disp_filled && !c->sp_fill) ASWCHK(dev_alloc(&c->sp_fill, S * 4));
+    c->sub = *o;
+    c->sub_on = true;
+    return ASW_OK;
+}
+
 int asw_set_graph(asw_ctx *c, int on) {
     if (!c) return ASW_E_INVALID;
     if (on && c->comm != COMM_NONE) return ASW_E_UNSUPPORTED;  // one shard, one stream
@@ -846,7 +924,8 @@ int asw_match_batch(asw_ctx *c, const uint8_t *left_rgba, const uint8_t *right_r
     if (!c || !left_rgba || !right_rgba || batch < 0 || (batch > 0 && !out)) return ASW_E_INVALID;
     const size_t img = frame_pixels(&c->p) * 4;
     for (int b = 0; b < batch; ++b)
-        ASWCHK(match_one(c, left_rgba + (size_t)b * img, right_rgba + (size_t)b * img, &out[b], t ? &t[b] : nullptr));
+        ASWCHK(match_one(c, left_rgba + (size_t)b * img, right_rgba + (size_t)b * img, &out[b], t ? &t[b] : nullptr,
+                         (size_t)b));
     return ASW_OK;
 }
 

@@ -28,7 +28,7 @@ import torch.distributed as dist
 
 from . import kernels as K
 from ._lib import AswParams
-from .pipeline import MatchResult, StereoMatcher
+from .pipeline import MatchResult, StereoMatcher, subpixel_lr_maps
 
 
 def plan_groups(ndisp: int, world: int, min_planes: int = 64) -> int:
@@ -62,6 +62,9 @@ class ShardOps(Protocol):
     def target_local(self, cost, key_ref): ...    # -> tkey, t1, t2
     def second(self, key_g, key_l, m1, m2): ...   # -> contribution
     def finalize(self, key, m2, tkey, t2): ...    # -> d_ref, conf_ref, d_tar, conf_tar, code_ref, code_tar
+    # sub-pixel maps (sharded_subpixel)
+    def subpixel_local(self, cost, key_g): ...    # -> nb [3][H][W]: owned neighbour planes of the winner, else +inf
+    def subpixel_finalize(self, key_g, nb): ...   # -> disp
 
 
 def _allreduce_min_factory(group=None) -> Callable[[torch.Tensor], torch.Tensor]:
@@ -72,16 +75,32 @@ def _allreduce_min_factory(group=None) -> Callable[[torch.Tensor], torch.Tensor]
     return reduce_min
 
 
-def sharded_wta(ops: ShardOps, cost, reduce_min: Callable, local: tuple | None = None) -> tuple:
+def sharded_wta(ops: ShardOps, cost, reduce_min: Callable, local: tuple | None = None,
+                key_out: list | None = None) -> tuple:
     """Exact WTA over a d-sharded cost volume (see module doc).  ``local``: the
-    (key, m1, m2) of ops.local(cost) when already computed."""
+    (key, m1, m2) of ops.local(cost) when already computed.  ``key_out``: a list that
+    receives the global key of the first all-reduce (what :func:`sharded_subpixel` reads)."""
     key, m1, m2 = ops.local(cost) if local is None else local
     key_g = reduce_min(key.clone())
+    if key_out is not None:
+        key_out.append(key_g)
     m2_g = reduce_min(ops.second(key_g, key, m1, m2))
     tkey, t1, t2 = ops.target_local(cost, key_g)
     tkey_g = reduce_min(tkey.clone())
     t2_g = reduce_min(ops.second(tkey_g, tkey, t1, t2))
     return ops.finalize(key_g, m2_g, tkey_g, t2_g)
+
+
+def sharded_subpixel(ops: ShardOps, cost, key_g, reduce_min: Callable):
+    """Exact sub-pixel map over a d-sharded volume, after the WTA's first all-reduce
+    (``key_g``): every shard offers the planes d-1, d, d+1 of the global winner d that it
+    owns (+inf for the others), ONE elementwise MIN all-reduce of that float32 [3][H][W]
+    array (costs are positive, one shard owns each plane) hands every rank the three
+    floats the unsharded kernel reads, and the finalize applies the same formula: the
+    result equals ``asw_subpixel`` on the whole volume bit for bit, also where the
+    winner's neighbours belong to another shard."""
+    nb = reduce_min(ops.subpixel_local(cost, key_g))
+    return ops.subpixel_finalize(key_g, nb)
 
 
 class HipShardOps:
@@ -102,6 +121,12 @@ class HipShardOps:
     def finalize(self, key, m2, tkey, t2):
         return K.wta_finalize(self.p, key, m2, tkey, t2)
 
+    def subpixel_local(self, cost, key_g):
+        return K.subpixel_local(self.p, cost, key_g)
+
+    def subpixel_finalize(self, key_g, nb):
+        return K.subpixel_finalize(self.p, key_g, nb)
+
 
 class ShardedStereoMatcher:
     """One rank's share of a d-sharded frame."""
@@ -115,7 +140,9 @@ class ShardedStereoMatcher:
         self.ops = HipShardOps(p)
         self.reduce_min = _allreduce_min_factory(group)
 
-    def match(self, left: torch.Tensor, right: torch.Tensor, events: list | None = None) -> MatchResult:
+    def match(self, left: torch.Tensor, right: torch.Tensor, events: list | None = None,
+              subpixel: bool = False) -> MatchResult:
+        """``subpixel``: also the float maps (one more MIN all-reduce, :func:`sharded_subpixel`)."""
         m = self.matcher
         if events is not None:
             events.append(("start", _record()))
@@ -124,7 +151,9 @@ class ShardedStereoMatcher:
             events.append(("support", _record()))
         cost = m.aggregate(events)
         # (m.local: the local scan, when the last pass ran it)
-        d_ref, conf_ref, d_tar, conf_tar, code_ref, code_tar = sharded_wta(self.ops, cost, self.reduce_min, m.local)
+        key_out: list = []
+        d_ref, conf_ref, d_tar, conf_tar, code_ref, code_tar = sharded_wta(self.ops, cost, self.reduce_min, m.local,
+                                                                           key_out if subpixel else None)
         if events is not None:
             events.append(("wta", _record()))
         lr = red = None
@@ -132,7 +161,12 @@ class ShardedStereoMatcher:
             lr, red = K.Constistency(self.p, d_ref, d_tar, code_ref, code_tar, conf_ref, conf_tar)
         if events is not None:
             events.append(("consistency", _record()))
-        return MatchResult(d_ref, conf_ref, d_tar, conf_tar, code_ref, code_tar, lr, red, cost)
+        res = MatchResult(d_ref, conf_ref, d_tar, conf_tar, code_ref, code_tar, lr, red, cost)
+        if subpixel:
+            res.disp = sharded_subpixel(self.ops, cost, key_out[0], self.reduce_min)
+            if lr is not None:
+                res.disp_lr, res.disp_filled = subpixel_lr_maps(self.p, res)
+        return res
 
 
 def _record():

@@ -23,7 +23,13 @@
 //     repeated id puts several shards on one GPU), and 16-bit disparity images
 //     (asw_wta_disparity16.png, asw_consistency16.png with 65535 = inconsistent) are
 //     written with --png16 and always when D > 256, where the 8-bit codes collide
-//     (the LR check then compares indices, ASW_LR_NATIVE).
+//     (the LR check then compares indices, ASW_LR_NATIVE);
+//   * --subpixel writes the float sub-pixel disparity of the left view
+//     (asw_set_subpixel): asw_disparity_sub.pfm (one-channel PFM, the LR-masked map
+//     with +inf where the check fails, the Middlebury convention; the unmasked map
+//     with --no-lr) and asw_disparity_sub16.png (16-bit grey, round(64 * the
+//     hole-filled map); the unmasked map with --no-lr), for D <= 1024.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -44,14 +50,17 @@ struct Options {
     int runs = 10, ndisp = 61, taps = 33, iters = 7, device = 0, refine = 6;
     std::vector<int> devices;  // --devices: one context over several GPUs
     float gamma_c = -1.0f, gamma_g = -1.0f, tau = -1.0f;
-    bool lab = false, lr = true, native_lr = false, png16 = false;
+    bool lab = false, lr = true, native_lr = false, png16 = false, subpixel = false;
 };
 
 void usage() {
     std::fprintf(stderr,
                  "usage: asw_stereo [--pics FILE] [--root DIR] [--runs N] [--ndisp D] [--taps T] [--iters R]\n"
                  "                  [--gamma-c G] [--gamma-g G] [--tau TAU] [--lab] [--no-lr] [--native-lr]\n"
-                 "                  [--refine K] [--device I | --devices I,J,...] [--png16] [--tsv FILE]\n");
+                 "                  [--refine K] [--device I | --devices I,J,...] [--png16] [--tsv FILE]\n"
+                 "                  [--subpixel]\n"
+                 "  --subpixel  float sub-pixel disparity (needs --ndisp <= 1024): asw_disparity_sub.pfm (LR-masked,\n"
+                 "              +inf = inconsistent) and asw_disparity_sub16.png (16-bit, 64 x the hole-filled map)\n");
 }
 
 bool parse(int argc, char **argv, Options &o) {
@@ -89,6 +98,7 @@ bool parse(int argc, char **argv, Options &o) {
             }
         }
         else if (a == "--png16") o.png16 = true;
+        else if (a == "--subpixel") o.subpixel = true;
         else if (a == "--lab") o.lab = true;
         else if (a == "--no-lr") o.lr = false;
         else if (a == "--native-lr") o.native_lr = true;
@@ -96,6 +106,10 @@ bool parse(int argc, char **argv, Options &o) {
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return false; }
     }
     if (o.runs < 1) o.runs = 1;
+    if (o.subpixel && o.ndisp > 1024) {  // 64 * (D - 1) must fit the 16-bit image
+        std::fprintf(stderr, "--subpixel needs --ndisp <= 1024\n");
+        return false;
+    }
     return true;
 }
 
@@ -212,6 +226,22 @@ int main(int argc, char **argv) {
         const size_t S = (size_t)p.width * p.height;
         std::vector<uint8_t> disp(S * 4), lr(S * 4), lr_red(S * 4), fin(S * 4), post(S * 4);
         std::vector<uint16_t> disp16(png16 ? S : 0), lr16(png16 ? S : 0);
+        // sub-pixel float maps: registered once, filled by every asw_match
+        std::vector<float> sub(o.subpixel ? S : 0), sub_lr(o.subpixel && p.lr_check ? S : 0),
+            sub_fill(o.subpixel && p.lr_check ? S : 0);
+        if (o.subpixel) {
+            asw_subpixel_outputs so;
+            so.disp = sub.data();
+            so.disp_lr = p.lr_check ? sub_lr.data() : nullptr;
+            so.disp_filled = p.lr_check ? sub_fill.data() : nullptr;
+            st = asw_set_subpixel(ctx, &so);
+            if (st != ASW_OK) {
+                std::fprintf(stderr, "%s: asw_set_subpixel: %s\n", folder.c_str(), asw_strerror(st));
+                ++failures;
+                asw_destroy(ctx);
+                continue;
+            }
+        }
         asw_outputs out;
         std::memset(&out, 0, sizeof out);
         out.disp_rgba = disp.data();
@@ -267,6 +297,21 @@ int main(int argc, char **argv) {
             e = asw_host::png_save16(dir + "/asw_wta_disparity16.png", disp16.data(), L.width, L.height);
             if (e.empty() && p.lr_check)
                 e = asw_host::png_save16(dir + "/asw_consistency16.png", lr16.data(), L.width, L.height);
+            if (!e.empty()) {
+                std::fprintf(stderr, "%s: %s\n", folder.c_str(), e.c_str());
+                ++failures;
+            }
+        }
+        if (o.subpixel) {
+            // PFM: the LR-masked map, invalid = +inf; PNG: round-to-nearest(64 * dense map)
+            std::vector<float> &pf = p.lr_check ? sub_lr : sub;
+            const std::vector<float> &dense = p.lr_check ? sub_fill : sub;
+            for (float &v : pf)
+                if (v != v) v = INFINITY;
+            std::vector<uint16_t> q(S);
+            for (size_t i = 0; i < S; ++i) q[i] = (uint16_t)std::nearbyintf(dense[i] * 64.0f);
+            e = asw_host::pfm_save(dir + "/asw_disparity_sub.pfm", pf.data(), L.width, L.height);
+            if (e.empty()) e = asw_host::png_save16(dir + "/asw_disparity_sub16.png", q.data(), L.width, L.height);
             if (!e.empty()) {
                 std::fprintf(stderr, "%s: %s\n", folder.c_str(), e.c_str());
                 ++failures;

@@ -320,6 +320,25 @@ std::string png_save16(const std::string &path, const uint16_t *data, unsigned w
     return ok ? std::string() : "short write " + path;
 }
 
+std::string pfm_save(const std::string &path, const float *data, unsigned w, unsigned h) {
+    if (!data || w == 0 || h == 0) return "pfm: empty image";
+    FILE *fp = std::fopen(path.c_str(), "wb");
+    if (!fp) return "cannot write " + path;
+    bool ok = std::fprintf(fp, "Pf\n%u %u\n-1.0\n", w, h) > 0;
+    std::vector<uint8_t> row((size_t)w * 4);
+    for (unsigned y = h; ok && y-- > 0;) {  // PFM stores the bottom row first
+        const float *src = data + (size_t)y * w;
+        for (unsigned x = 0; x < w; ++x) {  // little-endian on any host
+            uint32_t u;
+            std::memcpy(&u, &src[x], 4);
+            for (int b = 0; b < 4; ++b) row[(size_t)x * 4 + b] = (uint8_t)(u >> (8 * b));
+        }
+        ok = std::fwrite(row.data(), 1, row.size(), fp) == row.size();
+    }
+    std::fclose(fp);
+    return ok ? std::string() : "short write " + path;
+}
+
 std::string png_save(const std::string &path, const uint8_t *data, unsigned w, unsigned h, int channels) {
     std::vector<uint8_t> buf;
     std::string e = png_encode(data, w, h, channels, buf);

@@ -29,5 +29,8 @@ std::string png_save(const std::string &path, const uint8_t *data, unsigned w, u
 // 16-bit grey (colour type 0, depth 16): disparity maps past 256 levels
 std::string png_encode16(const uint16_t *data, unsigned w, unsigned h, std::vector<uint8_t> &out);
 std::string png_save16(const std::string &path, const uint16_t *data, unsigned w, unsigned h);
+// Portable Float Map, one channel ("Pf"), little-endian (scale -1.0), rows bottom to
+// top: the float disparity format of the Middlebury tools.  data is [h][w], top row first.
+std::string pfm_save(const std::string &path, const float *data, unsigned w, unsigned h);
 
 }  // namespace asw_host

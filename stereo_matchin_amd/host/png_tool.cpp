@@ -2,7 +2,8 @@
 //   png_tool decode IN.png OUT.raw   -> "W H" on stdout, RGBA8 bytes to OUT.raw
 //   png_tool encode IN.raw W H C OUT.png   (C = 1 grey8 or 4 RGBA8)
 //   png_tool encode16 IN.raw W H OUT.png   (host-order uint16 grey)
-//   png_tool fuzz SEED.png N S            -> decodes N mutants of SEED.png (seed S);
+//   png_tool pfm IN.raw W H OUT.pfm        (host-order float32 [H][W], top row first)
+//   png_tool fuzz SEED.png N S           -> decodes N mutants of SEED.png (seed S);
 //     run under the sanitizer build (make ASAN=1) a decoder bug aborts the process
 #include <zlib.h>
 
@@ -193,6 +194,20 @@ int main(int argc, char **argv) {
         }
         return 0;
     }
-    std::fprintf(stderr, "usage: png_tool decode IN.png OUT.raw | encode IN.raw W H C OUT.png | encode16 IN.raw W H OUT.png\n");
+    if (argc == 6 && !std::strcmp(argv[1], "pfm")) {
+        const unsigned w = (unsigned)std::atoi(argv[3]), h = (unsigned)std::atoi(argv[4]);
+        std::vector<float> buf((size_t)w * h);
+        FILE *f = std::fopen(argv[2], "rb");
+        if (!f || std::fread(buf.data(), 4, buf.size(), f) != buf.size()) return 1;
+        std::fclose(f);
+        const std::string e = asw_host::pfm_save(argv[5], buf.data(), w, h);
+        if (!e.empty()) {
+            std::fprintf(stderr, "%s\n", e.c_str());
+            return 1;
+        }
+        return 0;
+    }
+    std::fprintf(stderr, "usage: png_tool decode IN.png OUT.raw | encode IN.raw W H C OUT.png | encode16 IN.raw W H OUT.png"
+                         " | pfm IN.raw W H OUT.pfm\n");
     return 2;
 }

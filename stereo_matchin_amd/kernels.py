@@ -323,6 +323,59 @@ def wta_finalize(p: AswParams, key, m2, tkey, t2):
     return d_ref, conf_ref, d_tar, conf_tar, code_ref, code_tar
 
 
+# ------------------------------------------------------------- sub-pixel float maps
+# No reference counterpart (it writes 8-bit codes): the parabola offset of the winner
+# from its neighbouring planes, the LR-masked form and the row fill (include/asw.h).
+
+def subpixel(p: AswParams, cost: torch.Tensor, d_ref: torch.Tensor) -> torch.Tensor:
+    """asw_subpixel: float32 [H][W] sub-pixel disparity of a whole-range volume."""
+    _expect(cost, cost_shape(p), torch.float32, "cost")
+    _expect(d_ref, (p.height, p.width), torch.int32, "d_ref")
+    disp = torch.empty((p.height, p.width), dtype=torch.float32, device=cost.device)
+    _lib.check(_lib.lib().asw_subpixel(ctypes.byref(p), _ptr(cost), _ptr(d_ref), _ptr(disp), _stream(cost.device)),
+               "asw_subpixel")
+    return disp
+
+
+def subpixel_local(p: AswParams, cost: torch.Tensor, key_global: torch.Tensor) -> torch.Tensor:
+    """asw_subpixel_local: this shard's [3][H][W] neighbour costs of the global winner
+    (+inf where it does not own the plane), the operand of one MIN all-reduce."""
+    _expect(cost, cost_shape(p), torch.float32, "cost")
+    _expect(key_global, (p.height, p.width), torch.int64, "key_global")
+    nb = torch.empty((3, p.height, p.width), dtype=torch.float32, device=cost.device)
+    _lib.check(_lib.lib().asw_subpixel_local(ctypes.byref(p), _ptr(cost), _ptr(key_global), _ptr(nb),
+                                             _stream(cost.device)), "asw_subpixel_local")
+    return nb
+
+
+def subpixel_finalize(p: AswParams, key_global: torch.Tensor, nb: torch.Tensor) -> torch.Tensor:
+    """asw_subpixel_finalize: the sub-pixel map from the reduced neighbour costs."""
+    _expect(key_global, (p.height, p.width), torch.int64, "key_global")
+    _expect(nb, (3, p.height, p.width), torch.float32, "nb")
+    disp = torch.empty((p.height, p.width), dtype=torch.float32, device=nb.device)
+    _lib.check(_lib.lib().asw_subpixel_finalize(ctypes.byref(p), _ptr(key_global), _ptr(nb), _ptr(disp),
+                                                _stream(nb.device)), "asw_subpixel_finalize")
+    return disp
+
+
+def disp_mask(p: AswParams, disp, d_ref, d_tar, code_ref=None, code_tar=None) -> torch.Tensor:
+    """asw_disp_mask: disp where the LR check passes (p.lr_mode), NaN elsewhere."""
+    _expect(disp, (p.height, p.width), torch.float32, "disp")
+    out = torch.empty_like(disp)
+    _lib.check(_lib.lib().asw_disp_mask(ctypes.byref(p), _ptr(disp), _ptr(d_ref), _ptr(d_tar), _ptr(code_ref),
+                                        _ptr(code_tar), _ptr(out), _stream(disp.device)), "asw_disp_mask")
+    return out
+
+
+def disp_fill(p: AswParams, disp_lr: torch.Tensor) -> torch.Tensor:
+    """asw_disp_fill: NaN holes filled per row with the smaller valid neighbour."""
+    _expect(disp_lr, (p.height, p.width), torch.float32, "disp_lr")
+    out = torch.empty_like(disp_lr)
+    _lib.check(_lib.lib().asw_disp_fill(ctypes.byref(p), _ptr(disp_lr), _ptr(out), _stream(disp_lr.device)),
+               "asw_disp_fill")
+    return out
+
+
 # --------------------------------------------------------------------------- refinement
 # main.cpp:540-623: k x (asw_ref_v, asw_ref_h on both views, asw_WTA_REF,
 # Constistency), then Median.  Estimates are [2][H][W] f32 (value plane, den plane).

@@ -39,6 +39,10 @@ class MatchResult:
     lr_rgba: torch.Tensor | None       # consistency_error
     lr_red_rgba: torch.Tensor | None   # consistency_error_red (asw_consistency_pre-reff.png)
     cost: torch.Tensor        # final aggregated volume [H][W][Dp]
+    # sub-pixel float maps (match(..., subpixel=True)): float32 [H][W]
+    disp: torch.Tensor | None = None         # d_ref + parabola offset of the neighbouring planes
+    disp_lr: torch.Tensor | None = None      # disp where the LR check passes, NaN elsewhere
+    disp_filled: torch.Tensor | None = None  # disp_lr with its holes filled per row
 
 
 class StereoMatcher:
@@ -113,7 +117,9 @@ class StereoMatcher:
         return self.c0
 
     def match(self, left: torch.Tensor, right: torch.Tensor, lr_check: bool | None = None,
-              events: list | None = None) -> MatchResult:
+              events: list | None = None, subpixel: bool = False) -> MatchResult:
+        """``subpixel``: also the float maps ``disp`` and, with the LR check, ``disp_lr`` /
+        ``disp_filled`` (asw_subpixel, asw_disp_mask, asw_disp_fill)."""
         p = self.p
         if events is not None:
             events.append(("start", _record()))
@@ -132,7 +138,12 @@ class StereoMatcher:
             lr, red = K.Constistency(p, d_ref, d_tar, code_ref, code_tar, conf_ref, conf_tar)
         if events is not None:
             events.append(("consistency", _record()))
-        return MatchResult(d_ref, conf_ref, d_tar, conf_tar, code_ref, code_tar, lr, red, cost)
+        res = MatchResult(d_ref, conf_ref, d_tar, conf_tar, code_ref, code_tar, lr, red, cost)
+        if subpixel:
+            res.disp = K.subpixel(p, cost, d_ref)
+            if lr is not None:
+                res.disp_lr, res.disp_filled = subpixel_lr_maps(p, res)
+        return res
 
     def refine(self, res: MatchResult, left: torch.Tensor, right: torch.Tensor, rp=None) -> dict:
         """The refinement loop + median (main.cpp:540-623) after ``match`` (needs its LR
@@ -143,6 +154,12 @@ class StereoMatcher:
             raise ValueError("refinement starts from the consistency image: match() with lr_check")
         rp = _lib.default_refine_params() if rp is None else rp
         return K.refine(self.p, rp, left, right, res.cost, res.lr_rgba, res.code_tar, res.conf_ref, res.conf_tar)
+
+
+def subpixel_lr_maps(p: AswParams, res: MatchResult):
+    """(disp_lr, disp_filled) of a result that holds ``disp`` and went through the LR check."""
+    disp_lr = K.disp_mask(p, res.disp, res.d_ref, res.d_tar, res.code_ref, res.code_tar)
+    return disp_lr, K.disp_fill(p, disp_lr)
 
 
 def _record():
@@ -225,12 +242,14 @@ class FrameContext:
         return out, o
 
     def match(self, left_rgba: np.ndarray, right_rgba: np.ndarray, want_cost: bool = False,
-              want16: bool = False) -> dict:
-        return self.match_batch(left_rgba[None], right_rgba[None], want_cost, want16)[0]
+              want16: bool = False, subpixel: bool = False) -> dict:
+        return self.match_batch(left_rgba[None], right_rgba[None], want_cost, want16, subpixel)[0]
 
     def match_batch(self, lefts: np.ndarray, rights: np.ndarray, want_cost: bool = False,
-                    want16: bool = False) -> list[dict]:
-        """``asw_match_batch``: lefts / rights are [B][H][W][4] (or RGB) stacks."""
+                    want16: bool = False, subpixel: bool = False) -> list[dict]:
+        """``asw_match_batch``: lefts / rights are [B][H][W][4] (or RGB) stacks.
+        ``subpixel``: also the float maps ``disp_sub`` and, on a context with the LR check,
+        ``disp_sub_lr`` (NaN holes) / ``disp_sub_filled`` (asw_set_subpixel)."""
         H, W = self.p.height, self.p.width
         lefts = np.ascontiguousarray(np.stack([to_rgba(x) for x in lefts]))
         rights = np.ascontiguousarray(np.stack([to_rgba(x) for x in rights]))
@@ -239,8 +258,21 @@ class FrameContext:
         outs, os_ = zip(*[self._outputs(want_cost, want16) for _ in range(B)]) if B else ((), ())
         oarr = (_lib.AswOutputs * B)(*os_)
         tarr = (_lib.AswTimings * B)()
-        _lib.check(self.L.asw_match_batch(self.ctx, lefts.ctypes.data, rights.ctypes.data, B, oarr, tarr),
-                   "asw_match_batch")
+        sub = {}
+        if subpixel and B:
+            names = ("disp_sub", "disp_sub_lr", "disp_sub_filled") if self.p.lr_check else ("disp_sub",)
+            sub = {k: np.empty((B, H, W), np.float32) for k in names}
+            so = _lib.AswSubpixelOutputs(*[sub[k].ctypes.data for k in names])
+            _lib.check(self.L.asw_set_subpixel(self.ctx, ctypes.byref(so)), "asw_set_subpixel")
+        try:
+            _lib.check(self.L.asw_match_batch(self.ctx, lefts.ctypes.data, rights.ctypes.data, B, oarr, tarr),
+                       "asw_match_batch")
+        finally:
+            if sub:  # the registered arrays are this call's: off again
+                self.L.asw_set_subpixel(self.ctx, None)
+        for k, v in sub.items():
+            for b in range(B):
+                outs[b][k] = v[b]
         for b in range(B):
             outs[b]["timings"] = \
                 {f: getattr(tarr[b], f) for f, _ in tarr[b]._fields_}

@@ -1,0 +1,347 @@
+"""Sub-pixel float disparity maps on the GPU (include/asw.h: asw_subpixel,
+asw_subpixel_local / _finalize, asw_disp_mask, asw_disp_fill, asw_set_subpixel).
+
+Every comparison is on float32 bit patterns (NaN positions compared separately) against
+the numpy restatement of tests/subpixel_ref.py, which tests/test_subpixel.py pins.
+"""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import subpixel_ref as SR
+from conftest import ROOT, load_scene
+
+pytestmark = pytest.mark.gpu
+
+F = np.float32
+PKG = os.path.join(ROOT, "stereo_matchin_amd")
+CLI = os.path.join(PKG, "asw_stereo")
+SUB_KEYS = ("disp_sub", "disp_sub_lr", "disp_sub_filled")
+KEYS = ("d_ref", "d_tar", "conf_ref", "conf_tar", "disp_rgba", "lr_rgba", "lr_red_rgba", "disp16", "lr16")
+
+
+def _p(W, H, D, T=5, iters=1, **kw):
+    from stereo_matchin_amd import make_params
+    return make_params(W, H, ndisp=D, taps=T, iters=iters, **kw)
+
+
+def _rand_pair(seed, H, W, shift=6):
+    rng = np.random.default_rng(seed)
+    L = rng.integers(0, 256, (H, W, 4), dtype=np.uint8)
+    R = np.roll(L, -shift, axis=1).copy()
+    R[..., :3] = np.clip(R[..., :3].astype(int) + rng.integers(-4, 5, (H, W, 3)), 0, 255).astype(np.uint8)
+    L[..., 3] = R[..., 3] = 255
+    return L, R
+
+
+def _aggregated(gpu, H, W, D):
+    """The final aggregated volume [H][W][Dp] and d_ref of a synthetic.py pair: matched at
+    16 rows (make_pair paints regions of at least 8 rows), the first H rows kept."""
+    import torch
+    from stereo_matchin_amd import StereoMatcher
+    from stereo_matchin_amd.synthetic import make_pair
+    Lh, Rh, _ = make_pair(W, 16, D, 3)
+    res = StereoMatcher(_p(W, 16, D), gpu).match(torch.from_numpy(Lh).to(gpu), torch.from_numpy(Rh).to(gpu))
+    return res.cost[:H].contiguous(), res.d_ref[:H].contiguous()
+
+
+def _crafted(gpu, H, W, D, Dp, seed=9):
+    """Positive random costs, pixel i winning clearly at plane i % D (every plane wins
+    somewhere when H*W >= D: 0, D-1 and both ends of every shard); padding planes NaN."""
+    import torch
+    rng = np.random.default_rng(seed)
+    C = np.full((H, W, Dp), np.nan, F)
+    C[:, :, :D] = rng.uniform(1.0, 3.0, size=(H, W, D)).astype(F)
+    win = (np.arange(H * W) % D).reshape(H, W)
+    np.put_along_axis(C, win[..., None], rng.uniform(0.25, 0.75, size=(H, W, 1)).astype(F), axis=2)
+    if H * W > D:  # one exact tie with the right neighbour: off = +0.5
+        y, x = np.argwhere((win > 0) & (win < D - 1))[0]
+        C[y, x, win[y, x] + 1] = C[y, x, win[y, x]]
+    return torch.from_numpy(C).to(gpu), torch.from_numpy(win.astype(np.int32)).to(gpu)
+
+
+# ------------------------------------------------------------------ stage kernels
+
+@pytest.mark.parametrize("H,W,D", [(4, 70, 16), (3, 257, 61), (2, 64, 65), (4, 70, 256)])
+def test_subpixel_whole_volume(gpu, H, W, D):
+    from stereo_matchin_amd import kernels as K
+    p = _p(W, H, D)
+    Dp = K.cost_shape(p)[2]
+    for cost, d_ref in (_aggregated(gpu, H, W, D), _crafted(gpu, H, W, D, Dp)):
+        assert tuple(cost.shape) == (H, W, Dp)
+        disp = K.subpixel(p, cost, d_ref).cpu().numpy()
+        c, d = cost.cpu().numpy(), d_ref.cpu().numpy()
+        assert np.array_equal(d, np.argmin(c[:, :, :D], axis=2))  # the first argmin, as the definition needs
+        want = SR.subpixel_D(c, d, D)
+        assert SR.same_bits(disp, want)
+        assert not np.isnan(disp).any() and np.abs(disp - d).max() <= 0.5
+        assert (disp != d).any()
+
+
+@pytest.mark.parametrize("split", ["8x32", "3-way"])
+def test_subpixel_sharded_equals_whole(gpu, split):
+    """(4, 70, 256) as 8 shards of 32 planes (pitch 32) and as an uneven 3-way split:
+    local on every shard, elementwise minimum, finalize == asw_subpixel, bit for bit."""
+    import torch
+    from stereo_matchin_amd import kernels as K
+    from stereo_matchin_amd.distributed import shard_range
+    H, W, D = 4, 70, 256
+    p = _p(W, H, D)
+    n = 8 if split == "8x32" else 3
+    spans = [shard_range(D, r, n) for r in range(n)]
+    for cost, d_ref in (_aggregated(gpu, H, W, D), _crafted(gpu, H, W, D, 256)):
+        whole = K.subpixel(p, cost, d_ref)
+        key = K.wta_local(p, cost)[0]
+        assert np.array_equal(SR.key_index(key.cpu().numpy()), d_ref.cpu().numpy())
+        nb = None
+        for b, e in spans:
+            ps = p.copy()
+            ps.d_begin, ps.d_end = b, e
+            Dps = K.cost_shape(ps)[2]
+            assert Dps == (32 if split == "8x32" else 128)
+            cs = torch.full((H, W, Dps), float("nan"), dtype=torch.float32, device=gpu)
+            cs[:, :, :e - b] = cost[:, :, b:e]
+            part = K.subpixel_local(ps, cs, key)
+            pn = part.cpu().numpy()
+            assert SR.same_bits(pn, SR.local_neighbours(cs.cpu().numpy(), key.cpu().numpy(), b, e, D))
+            nb = part if nb is None else torch.minimum(nb, part)
+        got = K.subpixel_finalize(p, key, nb)
+        assert SR.same_bits(got.cpu().numpy(), whole.cpu().numpy())
+        assert SR.same_bits(got.cpu().numpy(), SR.subpixel_D(cost.cpu().numpy(), d_ref.cpu().numpy(), D))
+    dc = _crafted(gpu, H, W, D, 256)[1].cpu().numpy()
+    assert all((dc == e - 1).any() and (dc == b).any() for b, e in spans)  # winners on shard boundaries
+
+
+@pytest.mark.parametrize("lr_mode,W,H,D,shift", [(0, 90, 12, 24, 5), (1, 90, 12, 24, 5), (1, 600, 8, 512, 300)])
+def test_disp_mask_matches_lr16(gpu, lr_mode, W, H, D, shift):
+    """The NaN set of asw_disp_mask is the 0xFFFF set of the frame API's lr16 for the pair."""
+    import torch
+    from stereo_matchin_amd import FrameContext, StereoMatcher
+    from stereo_matchin_amd import kernels as K
+    Lh, Rh = _rand_pair(21, H, W, shift)
+    p = _p(W, H, D, 9, 1, lr_mode=lr_mode)
+    res = StereoMatcher(p, gpu).match(torch.from_numpy(Lh).to(gpu), torch.from_numpy(Rh).to(gpu))
+    disp = K.subpixel(p, res.cost, res.d_ref)
+    if lr_mode == 1:  # the native rule does not read the codes
+        got = K.disp_mask(p, disp, res.d_ref, res.d_tar).cpu().numpy()
+    else:
+        got = K.disp_mask(p, disp, res.d_ref, res.d_tar, res.code_ref, res.code_tar).cpu().numpy()
+    with FrameContext(p) as fc:
+        frame = fc.match(Lh, Rh, want16=True)
+    assert np.array_equal(frame["d_ref"], res.d_ref.cpu().numpy())
+    holes = frame["lr16"] == 0xFFFF
+    assert holes.any() and not holes.all()
+    assert np.array_equal(np.isnan(got), holes)
+    ok = SR.lr_pass(res.d_ref.cpu().numpy(), res.d_tar.cpu().numpy(), res.code_ref.cpu().numpy(),
+                    res.code_tar.cpu().numpy(), D, lr_mode)
+    assert SR.same_bits(got, SR.mask(disp.cpu().numpy(), ok))
+    if D == 512:
+        assert res.d_ref.max().item() > 256
+
+
+def _fill_rows(W, rng):
+    nan = F(np.nan)
+    base = rng.uniform(0.0, 60.0, size=W).astype(F)
+    rows = [base.copy(), np.full(W, nan, F)]
+    left = np.full(W, nan, F)
+    left[0] = base[0]
+    right = np.full(W, nan, F)
+    right[W - 1] = base[W - 1]
+    alt = base.copy()
+    alt[0::2] = nan
+    alt2 = base.copy()
+    alt2[1::2] = nan
+    run = base.copy()
+    n = min(300, max(W - 2, 0))
+    start = 200 if W >= 600 else 1  # W >= 600: columns 200..499 span the chunk boundary at 256
+    run[start:start + n] = nan
+    rnd = base.copy()
+    rnd[rng.uniform(size=W) < 0.7] = nan
+    edge = base.copy()  # invalid exactly up to, and from, a chunk / wave boundary
+    edge[:min(W, 256)] = nan
+    edge[min(W - 1, 320):] = nan
+    return rows + [left, right, alt, alt2, run, rnd, edge]
+
+
+@pytest.mark.parametrize("W", [1, 63, 64, 65, 257, 600, 1921])
+def test_disp_fill(gpu, W):
+    import torch
+    from stereo_matchin_amd import kernels as K
+    rows = _fill_rows(W, np.random.default_rng(W))
+    H = 3
+    p = _p(W, H, 16)
+    for i in range(0, len(rows), H):
+        img = np.stack(rows[i:i + H])
+        assert img.shape == (H, W)
+        got = K.disp_fill(p, torch.from_numpy(img).to(gpu)).cpu().numpy()
+        want = SR.fill(img)
+        assert not np.isnan(got).any()
+        assert SR.same_bits(got, want), (W, i)
+
+
+# ------------------------------------------------------------------ frame API
+
+def _stage_pipeline(gpu, p, Lh, Rh):
+    import torch
+    from stereo_matchin_amd import StereoMatcher
+    res = StereoMatcher(p, gpu).match(torch.from_numpy(Lh).to(gpu), torch.from_numpy(Rh).to(gpu), subpixel=True)
+    return {"disp_sub": res.disp.cpu().numpy(), "disp_sub_lr": res.disp_lr.cpu().numpy(),
+            "disp_sub_filled": res.disp_filled.cpu().numpy(), "res": res}
+
+
+def _same_sub(a, b):
+    for k in SUB_KEYS:
+        assert SR.same_bits(a[k], b[k]), k
+
+
+@pytest.fixture(scope="module")
+def small_frame(gpu):
+    """70 x 12, D 16, T 5, r 2 on a random pair: the one-shard frame with and without the
+    maps, the stage-API pipeline and the restatement, shared by the frame tests."""
+    from stereo_matchin_amd import FrameContext
+    Lh, Rh = _rand_pair(5, 12, 70, 4)
+    p = _p(70, 12, 16, 5, 2)
+    with FrameContext(p) as fc:
+        off = fc.match(Lh, Rh, want_cost=True, want16=True)
+        on = fc.match(Lh, Rh, want_cost=True, want16=True, subpixel=True)
+        again_off = fc.match(Lh, Rh, want16=True)
+    return {"p": p, "L": Lh, "R": Rh, "off": off, "on": on, "again_off": again_off}
+
+
+def test_frame_maps_equal_stage_pipeline_and_restatement(gpu, small_frame):
+    f = small_frame
+    on, off = f["on"], f["off"]
+    assert all(k not in off and k not in f["again_off"] for k in SUB_KEYS)
+    for k in KEYS:  # every other output equals the frame with subpixel off
+        assert np.array_equal(on[k], off[k], equal_nan=True), k
+        assert np.array_equal(f["again_off"][k], off[k], equal_nan=True), k
+    assert np.array_equal(on["cost"], off["cost"])
+    stage = _stage_pipeline(gpu, f["p"], f["L"], f["R"])
+    _same_sub(on, stage)
+    want = SR.subpixel_D(on["cost"], on["d_ref"], 16)
+    assert SR.same_bits(on["disp_sub"], want)
+    holes = on["lr16"] == 0xFFFF
+    assert holes.any()
+    assert SR.same_bits(on["disp_sub_lr"], SR.mask(want, ~holes))
+    assert SR.same_bits(on["disp_sub_filled"], SR.fill(SR.mask(want, ~holes)))
+    assert on["timings"]["total"] > 0
+
+
+def test_frame_sharded_and_graph_contexts_give_identical_maps(gpu, small_frame):
+    from stereo_matchin_amd import FrameContext
+    f = small_frame
+    with FrameContext(f["p"], devices=[0, 0, 0]) as fc:
+        assert len(fc.shards()) == 3
+        sharded = fc.match(f["L"], f["R"], want16=True, subpixel=True)
+        assert sharded["timings"]["exchange"] > 0
+    with FrameContext(f["p"], graph=True) as fc:
+        graphed = [fc.match(f["L"], f["R"], want16=True, subpixel=True) for _ in range(2)]  # capture, replay
+    for got in [sharded] + graphed:
+        _same_sub(got, f["on"])
+        for k in KEYS:
+            assert np.array_equal(got[k], f["on"][k], equal_nan=True), k
+
+
+def test_frame_rank_context_gives_identical_maps(gpu, small_frame):
+    """asw_create_rank (RCCL, one rank): the fifth all-reduce runs over ncclAllReduce."""
+    from stereo_matchin_amd import FrameContext, comm_unique_id
+    f = small_frame
+    with FrameContext(f["p"], devices=[0], rank=0, nranks=1, comm_id=comm_unique_id()) as fc:
+        got = fc.match(f["L"], f["R"], subpixel=True)
+    _same_sub(got, f["on"])
+
+
+def test_frame_maps_are_pre_refinement(gpu, small_frame):
+    from stereo_matchin_amd import FrameContext, _lib
+    f = small_frame
+    rp = _lib.default_refine_params(iters=2)
+    for devices in ([0], [0, 0, 0]):
+        with FrameContext(f["p"], devices=devices, refine=rp) as fc:
+            got = fc.match(f["L"], f["R"], subpixel=True)
+        assert "final_rgba" in got
+        _same_sub(got, f["on"])
+
+
+def test_frame_batch_equals_single_pairs(gpu):
+    from stereo_matchin_amd import FrameContext
+    pairs = [_rand_pair(40 + s, 12, 70, 3 + s) for s in range(2)]
+    p = _p(70, 12, 16, 5, 2)
+    with FrameContext(p) as fc:
+        single = [fc.match(L, R, subpixel=True) for L, R in pairs]
+        batch = fc.match_batch(np.stack([L for L, _ in pairs]), np.stack([R for _, R in pairs]), subpixel=True)
+    assert len(batch) == 2
+    for a, b in zip(batch, single):
+        _same_sub(a, b)
+        assert np.array_equal(a["d_ref"], b["d_ref"])
+    assert not SR.same_bits(batch[0]["disp_sub"], batch[1]["disp_sub"])
+
+
+def test_frame_without_lr_check(gpu):
+    """disp alone on a context without the LR check; the masked maps are ASW_E_INVALID there."""
+    import ctypes
+    from stereo_matchin_amd import FrameContext, _lib
+    Lh, Rh = _rand_pair(5, 12, 70, 4)
+    p = _p(70, 12, 16, 5, 2, lr_check=0)
+    with FrameContext(p) as fc:
+        got = fc.match(Lh, Rh, want_cost=True, subpixel=True)
+        assert "disp_sub_lr" not in got and "disp_sub_filled" not in got
+        assert SR.same_bits(got["disp_sub"], SR.subpixel_D(got["cost"], got["d_ref"], 16))
+        buf = np.empty((12, 70), F)
+        so = _lib.AswSubpixelOutputs(buf.ctypes.data, buf.ctypes.data, None)
+        assert fc.L.asw_set_subpixel(fc.ctx, ctypes.byref(so)) == _lib.ASW_E_INVALID
+
+
+# ------------------------------------------------------------------ tsukuba
+
+@pytest.fixture(scope="module")
+def tsukuba(gpu):
+    from stereo_matchin_amd import FrameContext
+    Lh, Rh, _ = load_scene("tsukuba")
+    p = _p(Lh.shape[1], Lh.shape[0], 16, 5, 7)
+    with FrameContext(p) as fc:
+        out = fc.match(Lh, Rh, want_cost=True, want16=True, subpixel=True)
+    return Lh, Rh, out
+
+
+def test_tsukuba_properties(tsukuba):
+    _, _, out = tsukuba
+    disp, d = out["disp_sub"], out["d_ref"]
+    assert SR.same_bits(disp, SR.subpixel_D(out["cost"], d, 16))
+    assert not np.isnan(disp).any()
+    off = disp - d.astype(F)
+    assert np.abs(off).max() <= 0.5
+    rounded = np.floor(disp + F(0.5)).astype(np.int32)
+    assert np.array_equal(rounded[off != F(0.5)], d[off != F(0.5)])
+    assert np.isfinite(out["disp_sub_filled"]).all()
+    holes = out["lr16"] == 0xFFFF
+    assert np.array_equal(np.isnan(out["disp_sub_lr"]), holes)
+    assert SR.same_bits(out["disp_sub_filled"][~holes], disp[~holes])
+    assert (off != 0).mean() > 0.5  # a sub-pixel map, not the integer one
+
+
+# ------------------------------------------------------------------ CLI
+
+def test_cli_subpixel_writes_pfm_and_png16(tsukuba, tmp_path):
+    PIL = pytest.importorskip("PIL.Image")
+    Lh, Rh, out = tsukuba
+    d = tmp_path / "tsukuba"
+    d.mkdir()
+    PIL.fromarray(Lh[..., :3]).save(d / "im1.png")
+    PIL.fromarray(Rh[..., :3]).save(d / "im5.png")
+    (tmp_path / "pics.txt").write_text("tsukuba/im1.png\ntsukuba/im5.png\n")
+    r = subprocess.run([CLI, "--pics", str(tmp_path / "pics.txt"), "--runs", "1", "--devices", "0,0", "--ndisp", "16",
+                        "--taps", "5", "--iters", "7", "--refine", "0", "--subpixel", "--tsv", str(tmp_path / "t.tsv")],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    pfm, scale = SR.read_pfm(d / "asw_disparity_sub.pfm")
+    assert scale == -1.0
+    want = np.where(np.isnan(out["disp_sub_lr"]), F(np.inf), out["disp_sub_lr"]).astype(F)
+    assert np.isinf(want).any()
+    assert np.array_equal(pfm.view(np.uint32), want.view(np.uint32))
+    png = np.asarray(PIL.open(d / "asw_disparity_sub16.png")).astype(np.int64)
+    assert np.array_equal(png, np.rint(out["disp_sub_filled"] * F(64.0)).astype(np.int64))
+    r = subprocess.run([CLI, "--pics", str(tmp_path / "pics.txt"), "--ndisp", "2048", "--subpixel"],
+                       capture_output=True, text=True, timeout=60)
+    assert r.returncode == 2 and "usage" in r.stderr
