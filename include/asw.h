@@ -94,7 +94,8 @@ int asw_last_hip_error(void); /* hipError_t of the last ASW_E_HIP */
  * Additive within revision 4 (no struct above changes its layout, no flag is added):
  *      the sub-pixel entry points asw_subpixel / asw_subpixel_local /
  *      asw_subpixel_finalize / asw_disp_mask / asw_disp_fill and asw_set_subpixel with
- *      its own asw_subpixel_outputs struct. */
+ *      its own asw_subpixel_outputs struct; the cross-based matcher's entry points
+ *      (asw_median3_rgba, asw_cross_*) and asw_set_cross with its own structs. */
 #define ASW_ABI_VERSION 4
 int asw_abi_version(void);
 
@@ -304,6 +305,60 @@ int asw_refine(const asw_params *p, const asw_refine_params *rp, const uint8_t *
                void *workspace, uint8_t *post_red_rgba, uint8_t *final_rgba, int32_t *d_ref, int32_t *d_tar,
                void *stream);
 
+/* ---- Cross-based matcher with orthogonal integral images: the reference's first method
+ * (main.cpp:243-411; K/median.cl, cross.cl, aggregation.cl, integral_h.cl, oii_hcross.cl,
+ * integral_v.cl, oii_vcross.cl, init_disparity.cl, disparity.cl), one call per reference
+ * kernel.  IEEE float32 in the reference's order.  Whole-volume
+ * p only (d_begin = 0, d_end = ndisp) with 2 <= ndisp <= 256 (8-bit codes); reads width,
+ * height and ndisp of p.  Volumes are [H][W][Dp] float32 like every cost volume; an arm
+ * map is [H][W] of four signed bytes (h-, h+, v-, v+) = (-a, +a, -a, +a), a in
+ * [1, arm_max] (the reference: four int planes). */
+typedef struct asw_cross_params {
+    int arm_max; /* longest arm (K/cross.cl:32-80: 25), 1..127                            */
+    int tau;     /* colour similarity in 8-bit units, 0..255: 25 is exactly the reference's
+                    |delta| / 255 < 0.10f (K/cross.cl:11-13)                              */
+} asw_cross_params;
+void asw_cross_params_default(asw_cross_params *cp);
+int asw_cross_params_check(const asw_params *p, const asw_cross_params *cp);
+size_t asw_cross_arm_bytes(const asw_params *p); /* H*W*4 */
+/* Median (K/median.cl:58-88, main.cpp:272-280) of an RGBA8 image: per channel, 3x3,
+ * clamp-to-edge, alpha 255.  in != out. */
+int asw_median3_rgba(const asw_params *p, const uint8_t *in_rgba, uint8_t *out_rgba, void *stream);
+/* Cross (K/cross.cl, main.cpp:284-292) on a median image.  Per direction: a = 1; for
+ * k = 1..arm_max, q = p + (k+1) dir is accepted (a = k) when it lies inside the image,
+ * k - a <= 1 and every colour channel is within tau of the ANCHOR p. */
+int asw_cross_arms(const asw_params *p, const asw_cross_params *cp, const uint8_t *med_rgba, int8_t *arms,
+                   void *stream);
+/* Aggregation (K/aggregation.cl, main.cpp:296-299): with f(c) = (float)c / 255.0f,
+ * cost[y][x][d] = (|f(Lr)-f(Rr)| + |f(Lg)-f(Rg)|) + |f(Lb)-f(Rb)| between medL(x, y) and
+ * medR(max(x-d, 0), y); padding planes are written 0. */
+int asw_cross_cost(const asw_params *p, const uint8_t *med_left_rgba, const uint8_t *med_right_rgba, float *cost,
+                   void *stream);
+/* Integral_h / Integral_v (main.cpp:304-306, :322-324), in place: the serial running sum
+ * along x (ASW_DIR_H, from x = 0) or y (ASW_DIR_V, from y = 0) of every plane < ndisp.
+ * Padding planes are neither read nor written. */
+int asw_cross_integral(const asw_params *p, int dir, float *vol, void *stream);
+/* Oii_hcross / Oii_vcross (K/oii_hcross.cl:13-31, main.cpp:312-317, :329-334).  With
+ * xr = max(0, x-d), m = max(armsR[y][xr].minus, armsL[y][x].minus) and
+ * pl = min(armsR[y][xr].plus, armsL[y][x].plus) of the direction's arms:
+ *   H: out[y][x][d] = (in[y][min(W-1, x+pl)][d] - in[y][max(0, x+m-1)][d]) / (float)(pl - m)
+ *   V: out[y][x][d] = (in[min(H-1, y+pl)][x][d] - in[max(0, y+m-1)][x][d]) / (float)(pl - m)
+ * (the reference's off-by-one at the lower end and its divisor, kept).  Padding planes of
+ * `in` are never read, those of `out` are written 0.  in != out. */
+int asw_cross_oii(const asw_params *p, int dir, const int8_t *arms_left, const int8_t *arms_right, const float *in,
+                  float *out, void *stream);
+/* Init_disparity (K/init_disparity.cl, main.cpp:339-341): d0 = the first strict minimum of
+ * vol over d in [0, ndisp), code0 = its 8-bit code (the rule of asw_wta).  d0 or code0 may
+ * be NULL. */
+int asw_cross_init(const asw_params *p, const float *vol, int32_t *d0, uint8_t *code0, void *stream);
+/* Disparity (K/disparity.cl, main.cpp:346-349): for pixel (x, y) with its own arms
+ * (vm, vp), every row i = vm..vp at yc = clamp(y+i), with (hm, hp) = armsL[yc][x], every
+ * j = hm..hp votes bin (int)(((float)code0[yc][clamp(x+j)] / 255.0f) * (float)(ndisp-1));
+ * d1 = the LAST bin with the largest count, code1 its 8-bit code.  d1 or code1 may be NULL;
+ * code0 != code1. */
+int asw_cross_vote(const asw_params *p, const uint8_t *code0, const int8_t *arms_left, int32_t *d1, uint8_t *code1,
+                   void *stream);
+
 /* tuning hook (benchmarks / kernel experiments): selects among compiled kernel
  * variants; returns the previous value, or ASW_E_INVALID for an unknown key.
  * Every variant computes bit-identical results. */
@@ -429,6 +484,30 @@ typedef struct asw_subpixel_outputs {
     float *disp_filled; /* disp_lr with the holes filled from the row's background  */
 } asw_subpixel_outputs;
 int asw_set_subpixel(asw_ctx *ctx, const asw_subpixel_outputs *o);
+/* The cross-based matcher (main.cpp:243-411) inside asw_match: caller-owned host arrays,
+ * any may be NULL.  asw_set_cross copies both structs and allocates the two arm maps, the
+ * two median images and the code maps once; every later asw_match runs the cross stages
+ * BEFORE the ASW stages, as the reference does, in the context's two cost volumes (which
+ * the ASW stages overwrite afterwards), and fills the registered arrays (asw_match_batch:
+ * pair b at offset b*H*W pixels of each array, timings[b]).  cp = NULL: off (the default;
+ * a frame then launches nothing new); o = NULL with cp set: ASW_E_INVALID.  The stages
+ * are never captured (asw_set_graph: they run on the stream before the replay) and their
+ * time is in no asw_timings column.  One-shard contexts only: asw_create_multi /
+ * asw_create_rank contexts with more than one shard return ASW_E_UNSUPPORTED (their
+ * volumes are shard-sized). */
+typedef struct asw_cross_timings { /* milliseconds, the columns of main.cpp:394-410 */
+    double median[2], cross[2];    /* left, right image                               */
+    double aggregation, integral_h, oii_h, integral_v, oii_v, init, vote;
+    double total;                  /* first median start to vote end                  */
+} asw_cross_timings;
+typedef struct asw_cross_outputs {
+    uint8_t *initial_rgba;      /* [H][W][4] cross_based_initial.png                          */
+    uint8_t *final_rgba;        /* [H][W][4] cross_based_disparity.png (3x3 median of the vote) */
+    uint8_t *median_left_rgba;  /* [H][W][4] median.png                                        */
+    int32_t *d_initial;         /* [H][W] initial disparity indices                            */
+    asw_cross_timings *timings;
+} asw_cross_outputs;
+int asw_set_cross(asw_ctx *ctx, const asw_cross_params *cp, const asw_cross_outputs *o);
 
 #ifdef __cplusplus
 }

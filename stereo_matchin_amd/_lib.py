@@ -110,6 +110,33 @@ class AswRefineParams(ctypes.Structure):
                 ("gamma_g", ctypes.c_float), ("alpha", ctypes.c_float)]
 
 
+class AswCrossParams(ctypes.Structure):
+    """Mirror of ``asw_cross_params`` (include/asw.h)."""
+
+    _fields_ = [("arm_max", ctypes.c_int), ("tau", ctypes.c_int)]
+
+
+class AswCrossTimings(ctypes.Structure):
+    """Mirror of ``asw_cross_timings``: the reference's columns (main.cpp:394-410), ms."""
+
+    _fields_ = [("median", ctypes.c_double * 2), ("cross", ctypes.c_double * 2)] + [
+        (n, ctypes.c_double) for n in ("aggregation", "integral_h", "oii_h", "integral_v", "oii_v", "init", "vote",
+                                       "total")]
+
+    def as_dict(self) -> dict:
+        d = {"median": list(self.median), "cross": list(self.cross)}
+        d.update({n: getattr(self, n) for n, _ in self._fields_[2:]})
+        return d
+
+
+class AswCrossOutputs(ctypes.Structure):
+    """Mirror of ``asw_cross_outputs``: caller-owned host arrays, any may be NULL."""
+
+    _fields_ = [("initial_rgba", ctypes.c_void_p), ("final_rgba", ctypes.c_void_p),
+                ("median_left_rgba", ctypes.c_void_p), ("d_initial", ctypes.c_void_p),
+                ("timings", ctypes.POINTER(AswCrossTimings))]
+
+
 class AswTimings(ctypes.Structure):
     _fields_ = [(n, ctypes.c_double) for n in (
         "raw_cost", "support", "v_pass_mean", "h_pass_mean", "aggregation_total", "wta",
@@ -122,6 +149,7 @@ _load_error: Exception | None = None
 P = ctypes.c_void_p
 PP = ctypes.POINTER(AswParams)
 RP = ctypes.POINTER(AswRefineParams)
+CP = ctypes.POINTER(AswCrossParams)
 I = ctypes.c_int
 
 # name -> (restype, argtypes).  Every function declared in include/asw.h.
@@ -177,6 +205,17 @@ SIGNATURES = {
     "asw_disp_mask": (I, [PP, P, P, P, P, P, P, P]),
     "asw_disp_fill": (I, [PP, P, P, P]),
     "asw_set_subpixel": (I, [P, P]),
+    "asw_cross_params_default": (None, [CP]),
+    "asw_cross_params_check": (I, [PP, CP]),
+    "asw_cross_arm_bytes": (ctypes.c_size_t, [PP]),
+    "asw_median3_rgba": (I, [PP, P, P, P]),
+    "asw_cross_arms": (I, [PP, CP, P, P, P]),
+    "asw_cross_cost": (I, [PP, P, P, P, P]),
+    "asw_cross_integral": (I, [PP, I, P, P]),
+    "asw_cross_oii": (I, [PP, I, P, P, P, P, P]),
+    "asw_cross_init": (I, [PP, P, P, P, P]),
+    "asw_cross_vote": (I, [PP, P, P, P, P, P]),
+    "asw_set_cross": (I, [P, CP, ctypes.POINTER(AswCrossOutputs)]),
     "asw_tune_set": (I, [I, I]),
     "asw_pass_kernel": (I, [I, I, ctypes.c_char_p, I]),
     "asw_device_name": (I, [I, ctypes.c_char_p, I]),
@@ -264,6 +303,17 @@ def default_refine_params(**kw) -> AswRefineParams:
             raise TypeError(f"unknown asw_refine_params field {k!r}")
         setattr(rp, k, v)
     return rp
+
+
+def default_cross_params(**kw) -> AswCrossParams:
+    """Reference settings of the cross-based matcher (arm_max 25, tau 25), overridable."""
+    cp = AswCrossParams()
+    _load().asw_cross_params_default(ctypes.byref(cp))
+    for k, v in kw.items():
+        if not hasattr(cp, k):
+            raise TypeError(f"unknown asw_cross_params field {k!r}")
+        setattr(cp, k, v)
+    return cp
 
 
 def disp_pitch(p: AswParams) -> int:

@@ -80,6 +80,16 @@ struct asw_ctx {
     asw_subpixel_outputs sub{};
     bool sub_on = false;
     float *sp_disp = nullptr, *sp_lr = nullptr, *sp_fill = nullptr;
+    // asw_set_cross: the cross-based matcher (main.cpp:243-411) ahead of the ASW stages, in
+    // shard 0's two cost volumes; its own maps and images (RGBA8) and timing events
+    asw_cross_params cp{};
+    asw_cross_outputs cro{};
+    bool cross_on = false;
+    uint8_t *cr_med_l = nullptr, *cr_med_r = nullptr, *cr_init = nullptr, *cr_final = nullptr;
+    int8_t *cr_arms_l = nullptr, *cr_arms_r = nullptr;
+    int32_t *cr_d0 = nullptr;
+    uint8_t *cr_code0 = nullptr, *cr_code1 = nullptr;
+    std::vector<hipEvent_t> cr_ev;
 };
 
 namespace {
@@ -309,10 +319,13 @@ int destroy_ctx(asw_ctx *c) {
     (void)hipSetDevice(c->sh[0].device);
     void *bufs[] = {c->red_tmp, c->d_ref, c->d_tar, c->conf_ref, c->conf_tar, c->code_ref, c->code_tar, c->lr,
                     c->lr_red, c->disp, c->disp16, c->lr16, c->rws, c->est, c->post_red, c->final_rgba,
-                    c->sp_disp, c->sp_lr, c->sp_fill};
+                    c->sp_disp, c->sp_lr, c->sp_fill, c->cr_med_l, c->cr_med_r, c->cr_init, c->cr_final,
+                    c->cr_arms_l, c->cr_arms_r, c->cr_d0, c->cr_code0, c->cr_code1};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (hipEvent_t e : c->ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->cr_ev)
         if (e) (void)hipEventDestroy(e);
     if (c->red_done) (void)hipEventDestroy(c->red_done);
     if (c->gx_main) (void)hipGraphExecDestroy(c->gx_main);
@@ -620,6 +633,77 @@ int subpixel_work(asw_ctx *c) {
     return ASW_OK;
 }
 
+// The cross-based matcher of a frame (asw_set_cross; main.cpp:272-354), on shard 0's
+// stream ahead of the ASW stages: it uploads the pair itself and borrows the shard's two
+// cost volumes, which the ASW stages overwrite afterwards.  The registered host arrays
+// receive pair `pair` of a batch.  Never captured into a graph.
+constexpr int kCrossEvents = 12;  // start + one per column of asw_cross_timings but the total
+
+int cross_work(asw_ctx *c, const uint8_t *left_rgba, const uint8_t *right_rgba, size_t pair) {
+    const asw_params *p = &c->p;
+    const size_t S = frame_pixels(p);
+    Shard &s0 = c->sh[0];
+    hipStream_t st = s0.stream;
+    std::vector<hipEvent_t> &ev = c->cr_ev;
+    const asw_cross_outputs &o = c->cro;
+    HIPCHK(hipMemcpyAsync(s0.left, left_rgba, S * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(s0.right, right_rgba, S * 4, hipMemcpyHostToDevice, st));
+    int e = 0;
+    HIPCHK(hipEventRecord(ev[e++], st));
+    ASWCHK(asw_median3_rgba(p, s0.left, c->cr_med_l, st));
+    HIPCHK(hipEventRecord(ev[e++], st));
+    ASWCHK(asw_median3_rgba(p, s0.right, c->cr_med_r, st));
+    HIPCHK(hipEventRecord(ev[e++], st));
+    ASWCHK(asw_cross_arms(p, &c->cp, c->cr_med_l, c->cr_arms_l, st));
+    HIPCHK(hipEventRecord(ev[e++], st));
+    ASWCHK(asw_cross_arms(p, &c->cp, c->cr_med_r, c->cr_arms_r, st));
+    HIPCHK(hipEventRecord(ev[e++], st));
+    ASWCHK(asw_cross_cost(p, c->cr_med_l, c->cr_med_r, s0.c0, st));
+    HIPCHK(hipEventRecord(ev[e++], st));
+    ASWCHK(asw_cross_integral(p, ASW_DIR_H, s0.c0, st));
+    HIPCHK(hipEventRecord(ev[e++], st));
+    ASWCHK(asw_cross_oii(p, ASW_DIR_H, c->cr_arms_l, c->cr_arms_r, s0.c0, s0.c1, st));
+    HIPCHK(hipEventRecord(ev[e++], st));
+    ASWCHK(asw_cross_integral(p, ASW_DIR_V, s0.c1, st));
+    HIPCHK(hipEventRecord(ev[e++], st));
+    ASWCHK(asw_cross_oii(p, ASW_DIR_V, c->cr_arms_l, c->cr_arms_r, s0.c1, s0.c0, st));
+    HIPCHK(hipEventRecord(ev[e++], st));
+    ASWCHK(asw_cross_init(p, s0.c0, c->cr_d0, c->cr_code0, st));
+    HIPCHK(hipEventRecord(ev[e++], st));
+    ASWCHK(asw_cross_vote(p, c->cr_code0, c->cr_arms_l, nullptr, c->cr_code1, st));
+    HIPCHK(hipEventRecord(ev[e++], st));
+    if (o.initial_rgba) {
+        hipLaunchKernelGGL(k_codes_to_rgba, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, (long long)S,
+                           c->cr_code0, reinterpret_cast<uchar4 *>(c->cr_init));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(o.initial_rgba + pair * S * 4, c->cr_init, S * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (o.final_rgba) {  // main.cpp:352-354: the Median of the voted code image
+        ASWCHK(asw_median3(p, c->cr_code1, 1, c->cr_final, st));
+        HIPCHK(hipMemcpyAsync(o.final_rgba + pair * S * 4, c->cr_final, S * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (o.median_left_rgba)
+        HIPCHK(hipMemcpyAsync(o.median_left_rgba + pair * S * 4, c->cr_med_l, S * 4, hipMemcpyDeviceToHost, st));
+    if (o.d_initial) HIPCHK(hipMemcpyAsync(o.d_initial + pair * S, c->cr_d0, S * 4, hipMemcpyDeviceToHost, st));
+    if (o.timings) {
+        HIPCHK(hipStreamSynchronize(st));
+        asw_cross_timings *t = o.timings + pair;
+        t->median[0] = ms_between(ev[0], ev[1]);
+        t->median[1] = ms_between(ev[1], ev[2]);
+        t->cross[0] = ms_between(ev[2], ev[3]);
+        t->cross[1] = ms_between(ev[3], ev[4]);
+        t->aggregation = ms_between(ev[4], ev[5]);
+        t->integral_h = ms_between(ev[5], ev[6]);
+        t->oii_h = ms_between(ev[6], ev[7]);
+        t->integral_v = ms_between(ev[7], ev[8]);
+        t->oii_v = ms_between(ev[8], ev[9]);
+        t->init = ms_between(ev[9], ev[10]);
+        t->vote = ms_between(ev[10], ev[11]);
+        t->total = ms_between(ev[0], ev[11]);
+    }
+    return ASW_OK;
+}
+
 // capture fn's work on stream st into *g / *gx (once), then launch it
 template <class F>
 int graph_run(hipStream_t st, hipGraph_t *g, hipGraphExec_t *gx, F &&fn) {
@@ -659,6 +743,7 @@ int match_one(asw_ctx *c, const uint8_t *left_rgba, const uint8_t *right_rgba, a
               e_ref = e_x + 4, e_d2h = e_x + 5, e_sub = e_x + 6;
     const bool graphed = c->graph && c->comm == COMM_NONE;
     HIPCHK(hipSetDevice(s0.device));
+    if (c->cross_on) ASWCHK(cross_work(c, left_rgba, right_rgba, pair));  // the reference's order: before ASW
     HIPCHK(hipEventRecord(ev[0], st));
     if (graphed) {
         HIPCHK(hipMemcpyAsync(s0.left, left_rgba, S * 4, hipMemcpyHostToDevice, st));
@@ -904,6 +989,37 @@ int asw_set_subpixel(asw_ctx *c, const asw_subpixel_outputs *o) {
     if (o->disp_filled && !c->sp_fill) ASWCHK(dev_alloc(&c->sp_fill, S * 4));
     c->sub = *o;
     c->sub_on = true;
+    return ASW_OK;
+}
+
+int asw_set_cross(asw_ctx *c, const asw_cross_params *cp, const asw_cross_outputs *o) {
+    if (!c) return ASW_E_INVALID;
+    if (!cp) {
+        c->cross_on = false;
+        c->cro = asw_cross_outputs{};
+        return ASW_OK;
+    }
+    if (!o) return ASW_E_INVALID;
+    if (c->n > 1 || c->nranks > 1) return ASW_E_UNSUPPORTED;  // shard-sized volumes
+    ASWCHK(asw_cross_params_check(&c->p, cp));
+    const size_t S = frame_pixels(&c->p);
+    HIPCHK(hipSetDevice(c->sh[0].device));
+    if (!c->cr_med_l) ASWCHK(dev_alloc(&c->cr_med_l, S * 4));
+    if (!c->cr_med_r) ASWCHK(dev_alloc(&c->cr_med_r, S * 4));
+    if (!c->cr_arms_l) ASWCHK(dev_alloc(&c->cr_arms_l, asw_cross_arm_bytes(&c->p)));
+    if (!c->cr_arms_r) ASWCHK(dev_alloc(&c->cr_arms_r, asw_cross_arm_bytes(&c->p)));
+    if (!c->cr_d0) ASWCHK(dev_alloc(&c->cr_d0, S * 4));
+    if (!c->cr_code0) ASWCHK(dev_alloc(&c->cr_code0, S));
+    if (!c->cr_code1) ASWCHK(dev_alloc(&c->cr_code1, S));
+    if (!c->cr_init) ASWCHK(dev_alloc(&c->cr_init, S * 4));
+    if (!c->cr_final) ASWCHK(dev_alloc(&c->cr_final, S * 4));
+    if (c->cr_ev.empty()) {
+        c->cr_ev.assign(kCrossEvents, nullptr);
+        for (hipEvent_t &e : c->cr_ev) HIPCHK(hipEventCreate(&e));
+    }
+    c->cp = *cp;
+    c->cro = *o;
+    c->cross_on = true;
     return ASW_OK;
 }
 

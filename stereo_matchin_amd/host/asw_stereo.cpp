@@ -28,7 +28,14 @@
 //     (asw_set_subpixel): asw_disparity_sub.pfm (one-channel PFM, the LR-masked map
 //     with +inf where the check fails, the Middlebury convention; the unmasked map
 //     with --no-lr) and asw_disparity_sub16.png (16-bit grey, round(64 * the
-//     hole-filled map); the unmasked map with --no-lr), for D <= 1024.
+//     hole-filled map); the unmasked map with --no-lr), for D <= 1024;
+//   * --cross runs the reference's first method, the cross-based matcher of
+//     main.cpp:243-411 (asw_set_cross), ahead of the ASW stages of every run and writes
+//     its three images (main.cpp:357-367): cross_based_initial.png,
+//     cross_based_disparity.png and median.png; its timing columns (main.cpp:394-411)
+//     then stand in front of the ASW columns of every TSV row, after the id and followed by
+//     two empty columns, as in the reference's files.  Without --cross the files and the
+//     TSV are unchanged.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -51,6 +58,8 @@ struct Options {
     std::vector<int> devices;  // --devices: one context over several GPUs
     float gamma_c = -1.0f, gamma_g = -1.0f, tau = -1.0f;
     bool lab = false, lr = true, native_lr = false, png16 = false, subpixel = false;
+    bool cross = false;  // --cross: the cross-based matcher first (main.cpp:243-411)
+    int cross_arm = -1, cross_tau = -1;
 };
 
 void usage() {
@@ -58,7 +67,9 @@ void usage() {
                  "usage: asw_stereo [--pics FILE] [--root DIR] [--runs N] [--ndisp D] [--taps T] [--iters R]\n"
                  "                  [--gamma-c G] [--gamma-g G] [--tau TAU] [--lab] [--no-lr] [--native-lr]\n"
                  "                  [--refine K] [--device I | --devices I,J,...] [--png16] [--tsv FILE]\n"
-                 "                  [--subpixel]\n"
+                 "                  [--subpixel] [--cross [--cross-arm N] [--cross-tau N]]\n"
+                 "  --cross     the reference's cross-based matcher first (one GPU, --ndisp <= 256): cross_based_initial.png,\n"
+                 "              cross_based_disparity.png, median.png, and its timing columns in front of the ASW columns of the TSV\n"
                  "  --subpixel  float sub-pixel disparity (needs --ndisp <= 1024): asw_disparity_sub.pfm (LR-masked,\n"
                  "              +inf = inconsistent) and asw_disparity_sub16.png (16-bit, 64 x the hole-filled map)\n");
 }
@@ -99,6 +110,9 @@ bool parse(int argc, char **argv, Options &o) {
         }
         else if (a == "--png16") o.png16 = true;
         else if (a == "--subpixel") o.subpixel = true;
+        else if (a == "--cross") o.cross = true;
+        else if (a == "--cross-arm") { if (!(v = next("--cross-arm"))) return false; o.cross_arm = std::atoi(v); }
+        else if (a == "--cross-tau") { if (!(v = next("--cross-tau"))) return false; o.cross_tau = std::atoi(v); }
         else if (a == "--lab") o.lab = true;
         else if (a == "--no-lr") o.lr = false;
         else if (a == "--native-lr") o.native_lr = true;
@@ -242,6 +256,29 @@ int main(int argc, char **argv) {
                 continue;
             }
         }
+        // cross-based matcher: registered once, run ahead of the ASW stages by every asw_match
+        std::vector<uint8_t> cr_init(o.cross ? S * 4 : 0), cr_fin(o.cross ? S * 4 : 0), cr_med(o.cross ? S * 4 : 0);
+        asw_cross_timings ct;
+        std::memset(&ct, 0, sizeof ct);
+        if (o.cross) {
+            asw_cross_params cp;
+            asw_cross_params_default(&cp);
+            if (o.cross_arm >= 0) cp.arm_max = o.cross_arm;
+            if (o.cross_tau >= 0) cp.tau = o.cross_tau;
+            asw_cross_outputs co;
+            std::memset(&co, 0, sizeof co);
+            co.initial_rgba = cr_init.data();
+            co.final_rgba = cr_fin.data();
+            co.median_left_rgba = cr_med.data();
+            co.timings = &ct;
+            st = asw_set_cross(ctx, &cp, &co);
+            if (st != ASW_OK) {
+                std::fprintf(stderr, "%s: asw_set_cross: %s\n", folder.c_str(), asw_strerror(st));
+                ++failures;
+                asw_destroy(ctx);
+                continue;
+            }
+        }
         asw_outputs out;
         std::memset(&out, 0, sizeof out);
         out.disp_rgba = disp.data();
@@ -253,7 +290,13 @@ int main(int argc, char **argv) {
         out.lr16 = png16 && p.lr_check ? lr16.data() : nullptr;
         if (tsv) {
             std::fprintf(tsv, "\n%s - %s\n", devname, folder.c_str());
-            std::fprintf(tsv, "id\taggr\tsupp_w\tv_aggr_mean\th_aggr_mean\ttotal aggregation\twta\tconsistency\t"
+            // --cross: the cross columns of main.cpp:394-411 between the id and the ASW columns,
+            // under the reference's own column names and with its two empty columns after them
+            std::fprintf(tsv, "id\t");
+            if (o.cross)
+                std::fprintf(tsv, "medL_solo\tmedR_solo\tmed_full\tcross_h\tcross_v\tcross_full\taggregation\tintegral_h\t"
+                                  "aggr_h\tintegral_v\taggr_v\tinit_disp\tfinal_disp\tcross method total\t\t\t");
+            std::fprintf(tsv, "aggr\tsupp_w\tv_aggr_mean\th_aggr_mean\ttotal aggregation\twta\tconsistency\t"
                               "total\trefine\th2d\td2h\texchange\n");
         }
         for (int run = 0; run < o.runs && st == ASW_OK; ++run) {
@@ -263,9 +306,16 @@ int main(int argc, char **argv) {
             if (st != ASW_OK) break;
             std::printf("run %d: total %.3f ms (aggregation %.3f, V %.3f, H %.3f per pass)\n", run, t.total,
                         t.aggregation_total, t.v_pass_mean, t.h_pass_mean);
+            if (tsv) std::fprintf(tsv, "%d\t", run);
+            if (tsv && o.cross)
+                std::fprintf(tsv, "%0.3f\t%0.3f\t%0.3f\t%0.3f\t%0.3f\t%0.3f\t%0.3f\t%0.3f\t%0.3f\t%0.3f\t%0.3f\t%0.3f\t"
+                                  "%0.3f\t%0.3f\t\t\t",
+                             ct.median[0], ct.median[1], ct.median[0] + ct.median[1], ct.cross[0], ct.cross[1],
+                             ct.cross[0] + ct.cross[1], ct.aggregation, ct.integral_h, ct.oii_h, ct.integral_v,
+                             ct.oii_v, ct.init, ct.vote, ct.total);
             if (tsv)
-                std::fprintf(tsv, "%d\t%0.3f\t%0.3f\t%0.3f\t%0.3f\t%0.3f\t%0.3f\t%0.3f\t%0.3f\t%0.3f\t%0.3f\t%0.3f\t%0.3f\n",
-                             run, t.raw_cost, t.support, t.v_pass_mean, t.h_pass_mean, t.aggregation_total, t.wta,
+                std::fprintf(tsv, "%0.3f\t%0.3f\t%0.3f\t%0.3f\t%0.3f\t%0.3f\t%0.3f\t%0.3f\t%0.3f\t%0.3f\t%0.3f\t%0.3f\n",
+                             t.raw_cost, t.support, t.v_pass_mean, t.h_pass_mean, t.aggregation_total, t.wta,
                              t.consistency, t.total, t.refine, t.h2d, t.d2h, t.exchange);
         }
         asw_destroy(ctx);
@@ -288,6 +338,15 @@ int main(int argc, char **argv) {
             if (!p.lr_check && w.img != &disp) continue;
             if (!refine && (w.img == &fin || w.img == &post)) continue;
             e = asw_host::png_save(dir + "/" + w.name, w.img->data(), L.width, L.height, 4);
+            if (!e.empty()) {
+                std::fprintf(stderr, "%s: %s\n", folder.c_str(), e.c_str());
+                ++failures;
+            }
+        }
+        if (o.cross) {  // main.cpp:357-367
+            e = asw_host::png_save(dir + "/cross_based_initial.png", cr_init.data(), L.width, L.height, 4);
+            if (e.empty()) e = asw_host::png_save(dir + "/cross_based_disparity.png", cr_fin.data(), L.width, L.height, 4);
+            if (e.empty()) e = asw_host::png_save(dir + "/median.png", cr_med.data(), L.width, L.height, 4);
             if (!e.empty()) {
                 std::fprintf(stderr, "%s: %s\n", folder.c_str(), e.c_str());
                 ++failures;

@@ -376,6 +376,83 @@ def disp_fill(p: AswParams, disp_lr: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ------------------------------------------------------------------ cross-based matcher
+# main.cpp:243-411: Median, Cross, Aggregation, Integral_h, Oii_hcross, Integral_v,
+# Oii_vcross, Init_disparity, Disparity.  Arm maps are int8 [H][W][4] = (h-, h+, v-, v+).
+
+def Median_rgba(p: AswParams, img: torch.Tensor) -> torch.Tensor:
+    """Per-channel 3x3 median (K/median.cl:58-88) of an RGBA8 image, alpha 255."""
+    _expect(img, (p.height, p.width, 4), torch.uint8, "img")
+    out = torch.empty_like(img)
+    _lib.check(_lib.lib().asw_median3_rgba(ctypes.byref(p), _ptr(img), _ptr(out), _stream(img.device)),
+               "asw_median3_rgba")
+    return out
+
+
+def Cross(p: AswParams, cp, med: torch.Tensor) -> torch.Tensor:
+    """Cross arms (K/cross.cl) of a median image: int8 [H][W][4]."""
+    _expect(med, (p.height, p.width, 4), torch.uint8, "med")
+    arms = torch.empty((p.height, p.width, 4), dtype=torch.int8, device=med.device)
+    _lib.check(_lib.lib().asw_cross_arms(ctypes.byref(p), ctypes.byref(cp), _ptr(med), _ptr(arms),
+                                         _stream(med.device)), "asw_cross_arms")
+    return arms
+
+
+def Aggregation(p: AswParams, med_l: torch.Tensor, med_r: torch.Tensor, out: torch.Tensor | None = None):
+    """AD cost volume (K/aggregation.cl) between the two median images."""
+    _expect(med_l, (p.height, p.width, 4), torch.uint8, "med_l")
+    _expect(med_r, (p.height, p.width, 4), torch.uint8, "med_r")
+    if out is None:
+        out = new_cost(p, med_l.device)
+    _expect(out, cost_shape(p), torch.float32, "out")
+    _lib.check(_lib.lib().asw_cross_cost(ctypes.byref(p), _ptr(med_l), _ptr(med_r), _ptr(out),
+                                         _stream(med_l.device)), "asw_cross_cost")
+    return out
+
+
+def Integral(p: AswParams, direction: int, vol: torch.Tensor) -> torch.Tensor:
+    """Integral_h / Integral_v: the serial running sum along x (DIR_H) or y (DIR_V), in place."""
+    _expect(vol, cost_shape(p), torch.float32, "vol")
+    _lib.check(_lib.lib().asw_cross_integral(ctypes.byref(p), direction, _ptr(vol), _stream(vol.device)),
+               "asw_cross_integral")
+    return vol
+
+
+def Oii_cross(p: AswParams, direction: int, arms_l: torch.Tensor, arms_r: torch.Tensor, vol: torch.Tensor,
+              out: torch.Tensor | None = None) -> torch.Tensor:
+    """Oii_hcross / Oii_vcross (K/oii_hcross.cl:13-31) of an integral volume."""
+    for a in (arms_l, arms_r):
+        _expect(a, (p.height, p.width, 4), torch.int8, "arms")
+    _expect(vol, cost_shape(p), torch.float32, "vol")
+    if out is None:
+        out = torch.empty_like(vol)
+    _expect(out, cost_shape(p), torch.float32, "out")
+    _lib.check(_lib.lib().asw_cross_oii(ctypes.byref(p), direction, _ptr(arms_l), _ptr(arms_r), _ptr(vol),
+                                        _ptr(out), _stream(vol.device)), "asw_cross_oii")
+    return out
+
+
+def Init_disparity(p: AswParams, vol: torch.Tensor):
+    """First strict minimum over d and its 8-bit code: ``(d0 int32, code0 uint8)``."""
+    _expect(vol, cost_shape(p), torch.float32, "vol")
+    d0 = torch.empty((p.height, p.width), dtype=torch.int32, device=vol.device)
+    code0 = torch.empty((p.height, p.width), dtype=torch.uint8, device=vol.device)
+    _lib.check(_lib.lib().asw_cross_init(ctypes.byref(p), _ptr(vol), _ptr(d0), _ptr(code0),
+                                         _stream(vol.device)), "asw_cross_init")
+    return d0, code0
+
+
+def Disparity(p: AswParams, code0: torch.Tensor, arms_l: torch.Tensor):
+    """Vote over the cross region (K/disparity.cl): ``(d1 int32, code1 uint8)``."""
+    _expect(code0, (p.height, p.width), torch.uint8, "code0")
+    _expect(arms_l, (p.height, p.width, 4), torch.int8, "arms_l")
+    d1 = torch.empty((p.height, p.width), dtype=torch.int32, device=code0.device)
+    code1 = torch.empty((p.height, p.width), dtype=torch.uint8, device=code0.device)
+    _lib.check(_lib.lib().asw_cross_vote(ctypes.byref(p), _ptr(code0), _ptr(arms_l), _ptr(d1), _ptr(code1),
+                                         _stream(code0.device)), "asw_cross_vote")
+    return d1, code1
+
+
 # --------------------------------------------------------------------------- refinement
 # main.cpp:540-623: k x (asw_ref_v, asw_ref_h on both views, asw_WTA_REF,
 # Constistency), then Median.  Estimates are [2][H][W] f32 (value plane, den plane).

@@ -156,6 +156,51 @@ class StereoMatcher:
         return K.refine(self.p, rp, left, right, res.cost, res.lr_rgba, res.code_tar, res.conf_ref, res.conf_tar)
 
 
+@dataclass
+class CrossResult:
+    median_l: torch.Tensor      # u8 [H][W][4] median.png
+    arms_l: torch.Tensor        # int8 [H][W][4] (h-, h+, v-, v+)
+    arms_r: torch.Tensor
+    d_initial: torch.Tensor     # int32 [H][W]
+    code_initial: torch.Tensor  # u8 [H][W] cross_based_initial.png grey values
+    d_final: torch.Tensor       # int32 [H][W] the vote, before the final median
+    code_final: torch.Tensor    # u8 [H][W]
+    final_rgba: torch.Tensor    # u8 [H][W][4] cross_based_disparity.png
+
+
+class CrossMatcher:
+    """The reference's cross-based matcher (main.cpp:243-411) on one GPU, stage by stage on
+    torch's current stream:
+
+        Median x 2 -> Cross x 2 -> Aggregation -> Integral_h -> Oii_hcross -> Integral_v
+        -> Oii_vcross -> Init_disparity -> Disparity -> Median
+
+    It owns two cost volumes, allocated once."""
+
+    def __init__(self, params: AswParams, device="cuda", cross_params=None):
+        self.p = params.copy()
+        self.cp = _lib.default_cross_params() if cross_params is None else cross_params
+        st = _lib.lib().asw_cross_params_check(ctypes.byref(self.p), ctypes.byref(self.cp))
+        if st != _lib.ASW_OK:
+            raise _lib.AswError(st, "asw_cross_params_check")
+        self.device = torch.device(device)
+        self.c0 = K.new_cost(self.p, self.device)
+        self.c1 = K.new_cost(self.p, self.device)
+
+    def match(self, left: torch.Tensor, right: torch.Tensor) -> CrossResult:
+        p, cp = self.p, self.cp
+        med_l, med_r = K.Median_rgba(p, left), K.Median_rgba(p, right)
+        arms_l, arms_r = K.Cross(p, cp, med_l), K.Cross(p, cp, med_r)
+        K.Aggregation(p, med_l, med_r, out=self.c0)
+        K.Integral(p, DIR_H, self.c0)
+        K.Oii_cross(p, DIR_H, arms_l, arms_r, self.c0, out=self.c1)
+        K.Integral(p, DIR_V, self.c1)
+        K.Oii_cross(p, DIR_V, arms_l, arms_r, self.c1, out=self.c0)
+        d0, code0 = K.Init_disparity(p, self.c0)
+        d1, code1 = K.Disparity(p, code0, arms_l)
+        return CrossResult(med_l, arms_l, arms_r, d0, code0, d1, code1, K.Median(p, code1))
+
+
 def subpixel_lr_maps(p: AswParams, res: MatchResult):
     """(disp_lr, disp_filled) of a result that holds ``disp`` and went through the LR check."""
     disp_lr = K.disp_mask(p, res.disp, res.d_ref, res.d_tar, res.code_ref, res.code_tar)
@@ -207,11 +252,40 @@ class FrameContext:
             arr = (ctypes.c_int * len(devices))(*devices)
             _lib.check(self.L.asw_create_multi(ctypes.byref(self.p), arr, len(devices), ctypes.byref(self.ctx)),
                        "asw_create_multi")
+        self.cross = None  # set_cross: (AswCrossParams, want timings)
         self.refine = refine is not None
         if refine is not None:  # an AswRefineParams: main.cpp:540-623 inside asw_match
             _lib.check(self.L.asw_set_refine(self.ctx, ctypes.byref(refine)), "asw_set_refine")
         if graph:  # asw_set_graph: capture the device work into HIP graphs, replay them
             _lib.check(self.L.asw_set_graph(self.ctx, 1), "asw_set_graph")
+
+    def set_cross(self, cross_params=True, timings: bool = True) -> None:
+        """``asw_set_cross``: run the cross-based matcher (main.cpp:243-411) ahead of the ASW
+        stages of every later match; its results arrive under ``cross_initial_rgba``,
+        ``cross_final_rgba``, ``cross_median_rgba``, ``cross_d_initial`` and
+        ``cross_timings``.  ``cross_params``: an AswCrossParams, True for the reference
+        values, None / False to turn it off again."""
+        if cross_params is None or cross_params is False:
+            _lib.check(self.L.asw_set_cross(self.ctx, None, None), "asw_set_cross")
+            self.cross = None
+            return
+        cp = _lib.default_cross_params() if cross_params is True else cross_params
+        # validated here with empty outputs; match_batch registers each call's arrays
+        _lib.check(self.L.asw_set_cross(self.ctx, ctypes.byref(cp), ctypes.byref(_lib.AswCrossOutputs())),
+                   "asw_set_cross")
+        self.cross = (cp, timings)
+
+    def _cross_outputs(self, B: int):
+        H, W = self.p.height, self.p.width
+        cr = {"cross_initial_rgba": np.empty((B, H, W, 4), np.uint8),
+              "cross_final_rgba": np.empty((B, H, W, 4), np.uint8),
+              "cross_median_rgba": np.empty((B, H, W, 4), np.uint8),
+              "cross_d_initial": np.empty((B, H, W), np.int32)}
+        tarr = (_lib.AswCrossTimings * B)() if self.cross[1] else None
+        co = _lib.AswCrossOutputs(cr["cross_initial_rgba"].ctypes.data, cr["cross_final_rgba"].ctypes.data,
+                                  cr["cross_median_rgba"].ctypes.data, cr["cross_d_initial"].ctypes.data,
+                                  ctypes.cast(tarr, ctypes.POINTER(_lib.AswCrossTimings)) if tarr else None)
+        return cr, tarr, co
 
     def shards(self) -> list[tuple[int, int]]:
         n, b, e = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
@@ -264,15 +338,24 @@ class FrameContext:
             sub = {k: np.empty((B, H, W), np.float32) for k in names}
             so = _lib.AswSubpixelOutputs(*[sub[k].ctypes.data for k in names])
             _lib.check(self.L.asw_set_subpixel(self.ctx, ctypes.byref(so)), "asw_set_subpixel")
+        cr, ctim = {}, None
+        if self.cross is not None and B:
+            cr, ctim, co = self._cross_outputs(B)
+            _lib.check(self.L.asw_set_cross(self.ctx, ctypes.byref(self.cross[0]), ctypes.byref(co)), "asw_set_cross")
         try:
             _lib.check(self.L.asw_match_batch(self.ctx, lefts.ctypes.data, rights.ctypes.data, B, oarr, tarr),
                        "asw_match_batch")
         finally:
             if sub:  # the registered arrays are this call's: off again
                 self.L.asw_set_subpixel(self.ctx, None)
-        for k, v in sub.items():
+            if cr:  # this call's arrays leave the context; the matcher stays on
+                self.L.asw_set_cross(self.ctx, ctypes.byref(self.cross[0]), ctypes.byref(_lib.AswCrossOutputs()))
+        for k, v in {**sub, **cr}.items():
             for b in range(B):
                 outs[b][k] = v[b]
+        if ctim is not None:
+            for b in range(B):
+                outs[b]["cross_timings"] = ctim[b].as_dict()
         for b in range(B):
             outs[b]["timings"] = \
                 {f: getattr(tarr[b], f) for f, _ in tarr[b]._fields_}

@@ -1,0 +1,367 @@
+"""The cross-based matcher's HIP kernels (stereo_matchin_amd/csrc/asw_cross.hip) against the
+numpy restatement tests/cross_ref.py, on bit patterns: float volumes bit for bit, arms,
+indices and codes exactly.  Stage by stage (each stage fed the restatement's input, the
+pitch padding pre-filled with NaN where the stage must not read it), the whole sequence,
+the frame API, the CLI, and the GPU output against the reference's committed images.
+"""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import cross_ref as CR
+from conftest import GOLDEN, ROOT, SCENES, load_scene
+
+pytestmark = pytest.mark.gpu
+
+MAX_MISMATCH_FRAC = 0.0025  # tests/test_cross.py: the ASW oracle's bound against the device images
+ART_ROWS = 341              # art is pinned on rows [0, 341)
+
+# (W, H, D): every arm clamps and d > x on most pixels; Dp 64 with three padding planes;
+# Dp 128; D 256; a long serial row; a long serial column
+SHAPES = [(7, 5, 4), (70, 9, 61), (33, 40, 65), (40, 12, 256), (1921, 3, 16), (3, 1030, 16)]
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.int32)
+
+
+def _pair(W, H, kind, seed):
+    """RGBA8 pair: 'random' noise (short arms) or 'piecewise' constant blocks with noise
+    inside tau (long arms that end at the block edges); right = left shifted by 2."""
+    rng = np.random.default_rng(seed)
+    if kind == "random":
+        L = rng.integers(0, 256, (H, W, 4), dtype=np.uint8)
+    else:
+        by, bx = max(2, H // 3), max(2, W // 4)
+        blocks = rng.integers(0, 256, ((H + by - 1) // by, (W + bx - 1) // bx, 3))
+        base = np.repeat(np.repeat(blocks, by, axis=0), bx, axis=1)[:H, :W]
+        L = np.zeros((H, W, 4), np.uint8)
+        L[..., :3] = np.clip(base + rng.integers(-4, 5, (H, W, 3)), 0, 255)
+    R = np.roll(L, -2, axis=1).copy()
+    R[..., :3] = np.clip(R[..., :3].astype(int) + rng.integers(-3, 4, (H, W, 3)), 0, 255)
+    L[..., 3] = R[..., 3] = 255
+    return np.ascontiguousarray(L), np.ascontiguousarray(R)
+
+
+@pytest.fixture(scope="module")
+def env(gpu):
+    import torch
+
+    import stereo_matchin_amd._lib as L
+    from stereo_matchin_amd import kernels as K
+    from stereo_matchin_amd import pipeline as P
+
+    class Env:
+        pass
+
+    e = Env()
+    e.torch, e.L, e.K, e.P, e.dev = torch, L, K, P, gpu
+    e.dev_t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(gpu)
+    return e
+
+
+_REF = {}
+
+
+def _ref(W, H, D, kind):
+    """the restatement of one case, computed once and shared (never modified)"""
+    key = (W, H, D, kind)
+    if key not in _REF:
+        L, R = _pair(W, H, kind, seed=W * 1000 + H * 10 + D)
+        _REF[key] = (L, R, CR.match(L, R, D, want_volumes=True))
+    return _REF[key]
+
+
+def _padded(e, p, vol, fill):
+    """[H][W][D] -> device [H][W][Dp], the padding planes holding `fill`"""
+    H, W, D = vol.shape
+    out = np.full((H, W, e.L.disp_pitch(p)), fill, np.float32)
+    out[:, :, :D] = vol
+    return e.dev_t(out)
+
+
+@pytest.mark.parametrize("kind", ["random", "piecewise"])
+@pytest.mark.parametrize("W,H,D", SHAPES)
+def test_stages_bit_exact(env, W, H, D, kind):
+    e, K = env, env.K
+    L, R, ref = _ref(W, H, D, kind)
+    p = e.L.default_params(W, H, ndisp=D)
+    cp = e.L.default_cross_params()
+    Dp = e.L.disp_pitch(p)
+    nan = np.float32(np.nan)
+    # Median, Cross
+    for img, key in ((L, "median_l"), (R, "median_r")):
+        assert np.array_equal(K.Median_rgba(p, e.dev_t(img)).cpu().numpy(), ref[key]), key
+    for med, key in (("median_l", "arms_l"), ("median_r", "arms_r")):
+        assert np.array_equal(K.Cross(p, cp, e.dev_t(ref[med])).cpu().numpy(), ref[key]), key
+    al, ar = e.dev_t(ref["arms_l"]), e.dev_t(ref["arms_r"])
+    # Aggregation: padding planes written 0
+    out = e.torch.full((H, W, Dp), float("nan"), dtype=e.torch.float32, device=e.dev)
+    c = K.Aggregation(p, e.dev_t(ref["median_l"]), e.dev_t(ref["median_r"]), out=out).cpu().numpy()
+    assert np.array_equal(_bits(c[:, :, :D]), _bits(ref["cost"])), "cost"
+    assert np.array_equal(_bits(c[:, :, D:]), np.zeros((H, W, Dp - D), np.int32)), "cost padding"
+    # integrals in place: padding (NaN) neither read nor written; oii: padding never read, written 0
+    for direction, d_, src, integ, oii in ((e.L.DIR_H, "h", "cost", "integral_h", "oii_h"),
+                                           (e.L.DIR_V, "v", "oii_h", "integral_v", "oii_v")):
+        v = K.Integral(p, direction, _padded(e, p, ref[src], nan)).cpu().numpy()
+        assert np.array_equal(_bits(v[:, :, :D]), _bits(ref[integ])), integ
+        assert np.isnan(v[:, :, D:]).all(), integ + " padding"
+        out = e.torch.full((H, W, Dp), float("nan"), dtype=e.torch.float32, device=e.dev)
+        t = K.Oii_cross(p, direction, al, ar, _padded(e, p, ref[integ], nan), out=out).cpu().numpy()
+        assert np.array_equal(_bits(t[:, :, :D]), _bits(ref[oii])), oii
+        assert np.array_equal(_bits(t[:, :, D:]), np.zeros((H, W, Dp - D), np.int32)), oii + " padding"
+    # Init_disparity: a padding plane that was read would win (-inf)
+    d0, code0 = K.Init_disparity(p, _padded(e, p, ref["oii_v"], -np.inf))
+    assert np.array_equal(d0.cpu().numpy(), ref["d_initial"])
+    assert np.array_equal(code0.cpu().numpy(), ref["code_initial"])
+    # Disparity and the final Median
+    d1, code1 = K.Disparity(p, e.dev_t(ref["code_initial"]), al)
+    assert np.array_equal(d1.cpu().numpy(), ref["d_final"])
+    assert np.array_equal(code1.cpu().numpy(), ref["code_final"])
+    fin = K.Median(p, e.dev_t(ref["code_final"])).cpu().numpy()
+    assert np.array_equal(fin[..., 0], ref["final"]) and (fin[..., 3] == 255).all()
+
+
+@pytest.mark.parametrize("W,H,D", SHAPES)
+def test_cross_matcher_sequence(env, W, H, D):
+    """CrossMatcher (the stage sequence on device buffers) equals the restatement end to end."""
+    e = env
+    L, R, ref = _ref(W, H, D, "piecewise")
+    res = e.P.CrossMatcher(e.L.default_params(W, H, ndisp=D), e.dev).match(e.dev_t(L), e.dev_t(R))
+    for got, key in ((res.median_l, "median_l"), (res.arms_l, "arms_l"), (res.arms_r, "arms_r"),
+                     (res.d_initial, "d_initial"), (res.code_initial, "code_initial"), (res.d_final, "d_final"),
+                     (res.code_final, "code_final")):
+        assert np.array_equal(got.cpu().numpy(), ref[key]), key
+    assert np.array_equal(res.final_rgba.cpu().numpy()[..., 0], ref["final"])
+
+
+def test_arm_and_tau_parameters(env):
+    e = env
+    L, _, _ = _ref(70, 9, 61, "piecewise")
+    p = e.L.default_params(70, 9, ndisp=61)
+    med = CR.median3_rgba(L)
+    for arm_max, tau in ((1, 25), (3, 0), (127, 255), (9, 40)):
+        cp = e.L.default_cross_params(arm_max=arm_max, tau=tau)
+        got = e.K.Cross(p, cp, e.dev_t(med)).cpu().numpy()
+        assert np.array_equal(got, CR.cross_arms(med, arm_max, tau)), (arm_max, tau)
+
+
+def test_constant_image(env):
+    """all arms are arm_max where the border allows, all costs 0, d0 = 0, the vote stays at bin 0"""
+    e = env
+    W, H, D = 80, 60, 61
+    img = np.full((H, W, 4), 90, np.uint8)
+    img[..., 3] = 255
+    res = e.P.CrossMatcher(e.L.default_params(W, H, ndisp=D), e.dev).match(e.dev_t(img), e.dev_t(img))
+    arms = res.arms_l.cpu().numpy().astype(int)
+    x, y = np.meshgrid(np.arange(W), np.arange(H))
+    lim = lambda room: np.clip(room - 1, 1, 25)  # noqa: E731  (largest k with k + 1 <= room, at least 1)
+    assert np.array_equal(arms[..., 0], -lim(x)) and np.array_equal(arms[..., 1], lim(W - 1 - x))
+    assert np.array_equal(arms[..., 2], -lim(y)) and np.array_equal(arms[..., 3], lim(H - 1 - y))
+    assert np.array_equal(res.arms_r.cpu().numpy(), res.arms_l.cpu().numpy())
+    assert (res.d_initial.cpu().numpy() == 0).all() and (res.d_final.cpu().numpy() == 0).all()
+    assert (res.final_rgba.cpu().numpy()[..., :3] == 0).all()
+    # a vote over equal counts resolves to the LAST bin: two codes, each on half of every window
+    p = e.L.default_params(W, H, ndisp=D)
+    cA, cB = int(CR.code_u8(5, D)), int(CR.code_u8(40, D))
+    code0 = np.where(x % 2 == 0, cA, cB).astype(np.uint8)
+    arms2 = np.tile(np.array([-2, 1, -1, 1], np.int8), (H, W, 1))  # 4 columns: 2 of each code inside the image
+    d1, _ = e.K.Disparity(p, e.dev_t(code0), e.dev_t(arms2))
+    want, _ = CR.vote(code0, arms2, D)
+    assert np.array_equal(d1.cpu().numpy(), want)
+    assert (want[:, 2:W - 1] == CR.code_index(cB, D)).all()
+
+
+def test_steps_above_tau_give_unit_arms(env):
+    e = env
+    W, H = 37, 23
+    x, y = np.meshgrid(np.arange(W), np.arange(H))
+    img = np.zeros((H, W, 4), np.uint8)
+    img[..., :3] = (50 * ((x + 2 * y) % 5))[..., None]  # every pixel at distance 2 or 3 differs by >= 50
+    img[..., 3] = 255
+    arms = e.K.Cross(e.L.default_params(W, H, ndisp=16), e.L.default_cross_params(), e.dev_t(img)).cpu().numpy()
+    assert np.array_equal(arms, np.tile(np.array([-1, 1, -1, 1], np.int8), (H, W, 1)))
+    assert np.array_equal(arms, CR.cross_arms(img))
+
+
+# ------------------------------------------------------------------------ frame API
+
+@pytest.fixture(scope="module")
+def tsukuba(env):
+    e = env
+    L, R, _ = load_scene("tsukuba")
+    ref = CR.match(L, R, 61)
+    p = e.L.default_params(L.shape[1], L.shape[0])
+    res = e.P.CrossMatcher(p, e.dev).match(e.dev_t(L), e.dev_t(R))
+    with e.P.FrameContext(p) as fc:
+        base = fc.match(L, R, want_cost=True, want16=True)
+    return L, R, ref, p, res, base
+
+
+ASW_KEYS = ("d_ref", "d_tar", "conf_ref", "conf_tar", "disp_rgba", "lr_rgba", "lr_red_rgba", "cost", "disp16", "lr16")
+
+
+def _check_cross_frame(out, res, ref):
+    assert np.array_equal(out["cross_d_initial"], ref["d_initial"])
+    assert np.array_equal(out["cross_d_initial"], res.d_initial.cpu().numpy())
+    assert np.array_equal(out["cross_initial_rgba"][..., 0], ref["code_initial"])
+    assert np.array_equal(out["cross_final_rgba"][..., 0], ref["final"])
+    assert np.array_equal(out["cross_final_rgba"], res.final_rgba.cpu().numpy())
+    assert np.array_equal(out["cross_median_rgba"], ref["median_l"])
+    for img in (out["cross_initial_rgba"], out["cross_final_rgba"]):
+        assert (img[..., 0] == img[..., 1]).all() and (img[..., 1] == img[..., 2]).all() and (img[..., 3] == 255).all()
+
+
+def _same_asw(out, base, keys=ASW_KEYS):
+    for k in keys:
+        assert np.array_equal(out[k].view(np.uint8), base[k].view(np.uint8)), k
+
+
+def test_frame_api_tsukuba(env, tsukuba):
+    e = env
+    L, R, ref, p, res, base = tsukuba
+    with e.P.FrameContext(p) as fc:
+        fc.set_cross(True)
+        out = fc.match(L, R, want_cost=True, want16=True)
+        _check_cross_frame(out, res, ref)
+        _same_asw(out, base)  # every ASW output bit-identical to a context without the cross stages
+        t = out["cross_timings"]
+        stages = t["median"] + t["cross"] + [t[k] for k in ("aggregation", "integral_h", "oii_h", "integral_v",
+                                                            "oii_v", "init", "vote")]
+        assert all(v > 0 for v in stages) and t["total"] >= max(stages)
+        assert abs(sum(stages) - t["total"]) <= 0.05 * t["total"] + 0.05
+        # off again: no cross key, the ASW outputs unchanged, and the arrays registered
+        # before are not written any more (a frame launches nothing new)
+        H, W = p.height, p.width
+        sent = {k: np.full((H, W, 4), 0xA5, np.uint8) for k in ("i", "f", "m")}
+        dsent = np.full((H, W), -77, np.int32)
+        co = e.L.AswCrossOutputs(sent["i"].ctypes.data, sent["f"].ctypes.data, sent["m"].ctypes.data,
+                                 dsent.ctypes.data, None)
+        cp = e.L.default_cross_params()
+        assert fc.L.asw_set_cross(fc.ctx, ctypes.byref(cp), ctypes.byref(co)) == e.L.ASW_OK
+        fc.set_cross(None)
+        off = fc.match(L, R, want_cost=True, want16=True)
+        assert not [k for k in off if k.startswith("cross_")]
+        _same_asw(off, base)
+        assert all((v == 0xA5).all() for v in sent.values()) and (dsent == -77).all()
+
+
+def test_frame_api_graph_and_refine(env, tsukuba):
+    """asw_set_graph on: the cross stages run ahead of the replay, same results (first
+    call captures, second replays); the refinement outputs are untouched as well."""
+    e = env
+    L, R, ref, p, res, base = tsukuba
+    rp = e.L.default_refine_params(iters=1)
+    with e.P.FrameContext(p, refine=rp) as plain:
+        want = plain.match(L, R)
+    with e.P.FrameContext(p, refine=rp, graph=True) as fc:
+        fc.set_cross(True)
+        for _ in range(2):
+            out = fc.match(L, R)
+            _check_cross_frame(out, res, ref)
+            _same_asw(out, want, ("d_ref", "d_tar", "conf_ref", "conf_tar", "disp_rgba", "lr_rgba", "lr_red_rgba",
+                                  "final_rgba", "post_red_rgba"))
+
+
+def test_frame_api_batch(env, tsukuba):
+    e = env
+    L, R, ref, p, res, base = tsukuba
+    L2, R2 = np.ascontiguousarray(L[::-1]), np.ascontiguousarray(R[::-1])
+    res2 = e.P.CrossMatcher(p, e.dev).match(e.dev_t(L2), e.dev_t(R2))
+    with e.P.FrameContext(p) as fc:
+        fc.set_cross(True)
+        outs = fc.match_batch(np.stack([L, L2]), np.stack([R, R2]))
+    _check_cross_frame(outs[0], res, ref)
+    assert np.array_equal(outs[1]["cross_d_initial"], res2.d_initial.cpu().numpy())
+    assert np.array_equal(outs[1]["cross_final_rgba"], res2.final_rgba.cpu().numpy())
+    assert np.array_equal(outs[1]["cross_median_rgba"], res2.median_l.cpu().numpy())
+    assert outs[1]["cross_timings"]["total"] > 0
+
+
+def test_two_shard_context_refuses(env, tsukuba):
+    e = env
+    p = tsukuba[3]
+    with e.P.FrameContext(p, devices=(0, 0)) as fc:
+        with pytest.raises(e.L.AswError) as ei:
+            fc.set_cross(True)
+        assert ei.value.status == e.L.ASW_E_UNSUPPORTED
+    with e.P.FrameContext(p) as fc:  # bad parameters, missing outputs
+        cp = e.L.default_cross_params(arm_max=200)
+        co = e.L.AswCrossOutputs()
+        assert fc.L.asw_set_cross(fc.ctx, ctypes.byref(cp), ctypes.byref(co)) == e.L.ASW_E_INVALID
+        assert fc.L.asw_set_cross(fc.ctx, ctypes.byref(e.L.default_cross_params()), None) == e.L.ASW_E_INVALID
+
+
+# ------------------------------------------------- GPU against the committed images
+
+@pytest.mark.parametrize("scene", SCENES)
+def test_gpu_reproduces_device_pngs(env, tsukuba, scene):
+    e = env
+    L, R, _ = load_scene(scene)
+    z = np.load(os.path.join(GOLDEN, f"cross_{scene}.npz"))
+    if scene == "tsukuba":
+        res = tsukuba[4]
+    else:
+        res = e.P.CrossMatcher(e.L.default_params(L.shape[1], L.shape[0]), e.dev).match(e.dev_t(L), e.dev_t(R))
+    rows = slice(0, ART_ROWS) if scene == "art" else slice(None)
+    for got, want, name in ((res.code_initial.cpu().numpy(), z["initial"], "cross_based_initial"),
+                            (res.final_rgba.cpu().numpy()[..., 0], z["final"], "cross_based_disparity")):
+        g, w = got[rows], want[rows]
+        mism = int((g != w).sum())
+        print(f"{scene} {name}: {mism} mismatching pixels of {g.size} ({100 * mism / g.size:.4f} %)")
+        assert mism / g.size <= MAX_MISMATCH_FRAC, name
+
+
+# ------------------------------------------------------------------------------ CLI
+
+PARENT_FILES = {"im1.png", "im5.png", "asw_wta_disparity.png", "asw_consistency.png", "asw_consistency_pre-reff.png",
+                "asw_disparity.png", "asw_consistency_post-reff.png"}
+PARENT_HEADER = ("id\taggr\tsupp_w\tv_aggr_mean\th_aggr_mean\ttotal aggregation\twta\tconsistency\ttotal\trefine\t"
+                 "h2d\td2h\texchange")
+REF_CROSS_COLUMNS = ["medL_solo", "medR_solo", "med_full", "cross_h", "cross_v", "cross_full", "aggregation",
+                     "integral_h", "aggr_h", "integral_v", "aggr_v", "init_disp", "final_disp", "cross method total"]
+
+
+def test_cli_cross(env, tsukuba, tmp_path):
+    PIL = pytest.importorskip("PIL.Image")
+    L, R, ref, p, res, base = tsukuba
+    cli = os.path.join(ROOT, "stereo_matchin_amd", "asw_stereo")
+    runs = {}
+    for name, extra in (("plain", []), ("cross", ["--cross"])):
+        d = tmp_path / name / "tsukuba"
+        d.mkdir(parents=True)
+        PIL.fromarray(L[..., :3]).save(d / "im1.png")
+        PIL.fromarray(R[..., :3]).save(d / "im5.png")
+        pics = tmp_path / name / "pics.txt"
+        pics.write_text("tsukuba/im1.png\ntsukuba/im5.png\n")
+        tsv = tmp_path / name / "t.tsv"
+        r = subprocess.run([cli, "--pics", str(pics), "--runs", "2", "--refine", "1", "--tsv", str(tsv)] + extra,
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr
+        runs[name] = (d, tsv.read_text().splitlines())
+    d, lines = runs["plain"]  # without --cross: the parent's files and TSV layout
+    assert {f.name for f in d.iterdir()} == PARENT_FILES
+    assert [ln for ln in lines if ln.startswith("id\t")] == [PARENT_HEADER]
+    rows = [ln for ln in lines if ln[:1].isdigit()]
+    assert len(rows) == 2 and all(len(ln.split("\t")) == 13 and ln.split("\t")[0] == str(i) for i, ln in enumerate(rows))
+    dc, lines_c = runs["cross"]
+    assert {f.name for f in dc.iterdir()} == PARENT_FILES | {"cross_based_initial.png", "cross_based_disparity.png",
+                                                            "median.png"}
+    for f in PARENT_FILES:  # the ASW images do not change
+        assert (d / f).read_bytes() == (dc / f).read_bytes(), f
+    rgba = lambda f: np.asarray(PIL.open(dc / f).convert("RGBA"))  # noqa: E731
+    assert np.array_equal(rgba("cross_based_initial.png")[..., 0], res.code_initial.cpu().numpy())
+    assert np.array_equal(rgba("cross_based_disparity.png"), res.final_rgba.cpu().numpy())
+    assert np.array_equal(rgba("median.png"), res.median_l.cpu().numpy())
+    # the reference's own layout (its committed TSV files): id, the 14 cross columns, two
+    # empty columns, the ASW columns
+    header = [ln for ln in lines_c if ln.startswith("id\t")]
+    assert header == ["id\t" + "\t".join(REF_CROSS_COLUMNS) + "\t\t\t" + PARENT_HEADER[3:]]
+    rows_c = [ln.split("\t") for ln in lines_c if ln[:1].isdigit()]
+    assert len(rows_c) == 2
+    for i, cols in enumerate(rows_c):
+        assert len(cols) == 1 + 14 + 2 + 12 and cols[0] == str(i) and cols[15] == cols[16] == ""
+        assert all(float(v) >= 0 for v in cols[1:15]) and float(cols[14]) > 0
