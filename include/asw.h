@@ -95,7 +95,9 @@ int asw_last_hip_error(void); /* hipError_t of the last ASW_E_HIP */
  *      the sub-pixel entry points asw_subpixel / asw_subpixel_local /
  *      asw_subpixel_finalize / asw_disp_mask / asw_disp_fill and asw_set_subpixel with
  *      its own asw_subpixel_outputs struct; the cross-based matcher's entry points
- *      (asw_median3_rgba, asw_cross_*) and asw_set_cross with its own structs. */
+ *      (asw_median3_rgba, asw_cross_*) and asw_set_cross with its own structs; the census /
+ *      AD-census matching cost (asw_census_*, asw_census, asw_census_cost, asw_census_cost16,
+ *      asw_census16_supported) and asw_set_census with its own asw_census_params struct. */
 #define ASW_ABI_VERSION 4
 int asw_abi_version(void);
 
@@ -121,12 +123,60 @@ int asw_raw_cost(const asw_params *p, const uint8_t *left_rgba, const uint8_t *r
  * tad_tau (or tad_tau < 0): ASW_E_UNSUPPORTED.  asw_aggregate_pass_den16 reads it as the
  * first V pass (main.cpp:494-500); the float values it converts are the ones
  * asw_raw_cost writes, so every output is bit-identical.  asw_raw16_supported: 1 when
- * both are built for p (that tad_tau, a ring tap count, iters >= 1), else 0. */
+ * both are built for p (that tad_tau, a ring tap count, iters >= 1), else 0.  The pass
+ * itself never reads tad_tau (it needs a ring tap count and iters >= 1, else
+ * ASW_E_UNSUPPORTED): it also reads asw_census_cost16's volume (integers <= 65535). */
 int asw_raw_cost16(const asw_params *p, const uint8_t *left_rgba, const uint8_t *right_rgba, uint16_t *cost,
                    void *stream);
 int asw_aggregate_pass_den16(const asw_params *p, const float *wvl, const float *wvr, const uint16_t *cin16,
                              float *cout, float *den, int den_mode, void *stream); /* V; den_mode NONE or WRITE */
 int asw_raw16_supported(const asw_params *p);
+
+/* ---- census / AD-census matching cost (no reference counterpart: the reference's only
+ * raw cost is the RGB AD, which a gain or offset between the two views breaks).  Every
+ * operation is an integer one but the two float operations of the float form
+ * (DESIGN.md §Census).
+ *   luma    Y = (77 R + 150 G + 29 B + 128) >> 8, 0..255 (alpha ignored)
+ *   census  uint64 per pixel over a win_w x win_h window (each of 3, 5, 7, 9 with
+ *           win_w * win_h - 1 <= 64: every pair but 9x9; default 9x7 = 62 bits).  The
+ *           neighbours are enumerated row-major (dy = -rh..rh, within a row dx = -rw..rw,
+ *           the centre skipped); neighbour n (0-based) sets bit n (LSB first) when
+ *           Y(clamp(x+dx), clamp(y+dy)) < Y(x, y) (strict; clamp-to-edge); upper bits 0.
+ *   cost    with xr = max(x - d, 0), d = d_begin + k (as asw_raw_cost),
+ *           AD = |dR|+|dG|+|dB| of L(x, y) and R(xr, y), ham = popcount(cenL(x, y) ^ cenR(xr, y))
+ *           and the integer weights ad_weight w_a >= 0, census_weight w_c >= 1:
+ *     float   cost = fminf((float)AD, tad_tau) * (float)w_a + (float)(w_c * ham)
+ *             (one float multiply, then one float add, no fma); w_a = 0: the AD term is
+ *             not formed, tad_tau is not read, cost = (float)(w_c * ham)
+ *     uint16  w_a * min(AD, tau) + w_c * ham as an integer: defined when w_a = 0 or
+ *             tad_tau >= 765 or integral (asw_raw_cost16's rule), else ASW_E_UNSUPPORTED.
+ *             Its float value equals the float form bit for bit.
+ *           Padding planes k >= d_end - d_begin are written 0.
+ * asw_census_params_check (ASW_E_INVALID otherwise): p passes asw_params_check, the window
+ * rule, 0 <= w_a <= 64, 1 <= w_c <= 1024, tad_tau >= 0 when w_a > 0, and
+ * w_a * min(765, ceil(tad_tau)) + w_c * (win_w * win_h - 1) <= 65535.
+ * asw_census16_supported: 1 when asw_census_cost16 and the first V pass over its volume
+ * (asw_aggregate_pass_den16) are built for (p, cp): the tau rule above, a ring tap count,
+ * iters >= 1 (asw_raw16_supported's conditions), else 0. */
+typedef struct asw_census_params {
+    int win_w, win_h;   /* census window (odd, 3..9, not 9x9); default 9 x 7            */
+    int ad_weight;      /* w_a: 0..64; 0 = census only; default 1                       */
+    int census_weight;  /* w_c: 1..1024; default 8                                      */
+} asw_census_params;
+void asw_census_params_default(asw_census_params *cp);
+int asw_census_params_check(const asw_params *p, const asw_census_params *cp);
+size_t asw_census_bytes(const asw_params *p); /* H*W*8 */
+/* the census codes [H][W] uint64 of an RGBA8 image */
+int asw_census(const asw_params *p, const asw_census_params *cp, const uint8_t *img_rgba, uint64_t *census,
+               void *stream);
+/* the cost volume [H][W][Dp] of p's planes from both images and their census codes */
+int asw_census_cost(const asw_params *p, const asw_census_params *cp, const uint8_t *left_rgba,
+                    const uint8_t *right_rgba, const uint64_t *cen_left, const uint64_t *cen_right, float *cost,
+                    void *stream);
+int asw_census_cost16(const asw_params *p, const asw_census_params *cp, const uint8_t *left_rgba,
+                      const uint8_t *right_rgba, const uint64_t *cen_left, const uint64_t *cen_right, uint16_t *cost,
+                      void *stream);
+int asw_census16_supported(const asw_params *p, const asw_census_params *cp);
 
 /* support-weight table (the exp of K/asw_vsupport.cl:22-25 for every (|delta|, SAD)) */
 int asw_support_lut(const asw_params *p, float *lut, void *stream);
@@ -508,6 +558,21 @@ typedef struct asw_cross_outputs {
     asw_cross_timings *timings;
 } asw_cross_outputs;
 int asw_set_cross(asw_ctx *ctx, const asw_cross_params *cp, const asw_cross_outputs *o);
+/* The census / AD-census cost in place of the AD raw cost of later asw_match calls
+ * (cp = NULL: off, the default; a frame then launches and allocates nothing new).
+ * asw_set_census checks cp against the context (asw_census_params_check), copies it and
+ * allocates the two census maps of every shard once (freed at asw_destroy).  A shard then
+ * runs asw_census on both images and asw_census_cost16 into its raw-cost volume where it
+ * would have run asw_raw_cost16 (the first V pass stays asw_aggregate_pass_den16), and
+ * asw_census_cost elsewhere (ASW_FLAG_RAW_F32, a non-integral tad_tau with w_a > 0, a tap
+ * count without a ring kernel).  The three launches are timed in asw_timings.raw_cost.
+ * Every context kind works: each shard repeats the d-independent transform and computes its
+ * own planes, with no new collective (with asw_create_rank every rank must switch census
+ * alike, or the ranks aggregate different costs).  With asw_set_graph on the launches are
+ * inside the captured frame: asw_set_census drops a captured frame graph, the next
+ * asw_match captures again.  Refinement, the sub-pixel maps, the LR modes and the
+ * cross-based stages (which keep their own cost) are untouched. */
+int asw_set_census(asw_ctx *ctx, const asw_census_params *cp);
 
 #ifdef __cplusplus
 }

@@ -116,6 +116,17 @@ class AswCrossParams(ctypes.Structure):
     _fields_ = [("arm_max", ctypes.c_int), ("tau", ctypes.c_int)]
 
 
+class AswCensusParams(ctypes.Structure):
+    """Mirror of ``asw_census_params`` (include/asw.h): window and the integer weights of
+    ``w_a * min(AD, tau) + w_c * hamming``."""
+
+    _fields_ = [("win_w", ctypes.c_int), ("win_h", ctypes.c_int), ("ad_weight", ctypes.c_int),
+                ("census_weight", ctypes.c_int)]
+
+    def copy(self) -> "AswCensusParams":
+        return AswCensusParams(self.win_w, self.win_h, self.ad_weight, self.census_weight)
+
+
 class AswCrossTimings(ctypes.Structure):
     """Mirror of ``asw_cross_timings``: the reference's columns (main.cpp:394-410), ms."""
 
@@ -150,6 +161,7 @@ P = ctypes.c_void_p
 PP = ctypes.POINTER(AswParams)
 RP = ctypes.POINTER(AswRefineParams)
 CP = ctypes.POINTER(AswCrossParams)
+NP = ctypes.POINTER(AswCensusParams)
 I = ctypes.c_int
 
 # name -> (restype, argtypes).  Every function declared in include/asw.h.
@@ -216,6 +228,14 @@ SIGNATURES = {
     "asw_cross_init": (I, [PP, P, P, P, P]),
     "asw_cross_vote": (I, [PP, P, P, P, P, P]),
     "asw_set_cross": (I, [P, CP, ctypes.POINTER(AswCrossOutputs)]),
+    "asw_census_params_default": (None, [NP]),
+    "asw_census_params_check": (I, [PP, NP]),
+    "asw_census_bytes": (ctypes.c_size_t, [PP]),
+    "asw_census": (I, [PP, NP, P, P, P]),
+    "asw_census_cost": (I, [PP, NP, P, P, P, P, P, P]),
+    "asw_census_cost16": (I, [PP, NP, P, P, P, P, P, P]),
+    "asw_census16_supported": (I, [PP, NP]),
+    "asw_set_census": (I, [P, NP]),
     "asw_tune_set": (I, [I, I]),
     "asw_pass_kernel": (I, [I, I, ctypes.c_char_p, I]),
     "asw_device_name": (I, [I, ctypes.c_char_p, I]),
@@ -314,6 +334,25 @@ def default_cross_params(**kw) -> AswCrossParams:
             raise TypeError(f"unknown asw_cross_params field {k!r}")
         setattr(cp, k, v)
     return cp
+
+
+def default_census_params(**kw) -> AswCensusParams:
+    """The default census cost (9 x 7 window, ad_weight 1, census_weight 8), overridable."""
+    cp = AswCensusParams()
+    _load().asw_census_params_default(ctypes.byref(cp))
+    for k, v in kw.items():
+        if not hasattr(cp, k):
+            raise TypeError(f"unknown asw_census_params field {k!r}")
+        setattr(cp, k, v)
+    return cp
+
+
+def census_params_of(census) -> AswCensusParams | None:
+    """The ``census=`` keyword of the matchers: None / False (off), True (the defaults) or
+    an AswCensusParams."""
+    if census is None or census is False:
+        return None
+    return default_census_params() if census is True else census.copy()
 
 
 def disp_pitch(p: AswParams) -> int:

@@ -47,6 +47,8 @@ struct Shard {
     hipEvent_t ready = nullptr;  // COMM_LOCAL: this shard's operand is complete
     float *ref_l = nullptr, *ref_r = nullptr;  // sharded refinement, shards > 0: the per-view estimates
     float *nb = nullptr;  // asw_set_subpixel on a sharded frame: [3][S] neighbour costs of the winner
+    uint64_t *cen_l = nullptr, *cen_r = nullptr;  // asw_set_census: the census codes of both images, [H][W]
+    bool census16 = false;  // census on: the costs as uint16 in c0 (asw_census_cost16 + asw_aggregate_pass_den16)
 };
 
 }  // namespace
@@ -90,6 +92,9 @@ struct asw_ctx {
     int32_t *cr_d0 = nullptr;
     uint8_t *cr_code0 = nullptr, *cr_code1 = nullptr;
     std::vector<hipEvent_t> cr_ev;
+    // asw_set_census: the census / AD-census cost in place of the AD raw cost
+    asw_census_params cen{};
+    bool census_on = false;
 };
 
 namespace {
@@ -252,7 +257,7 @@ void free_shard(Shard &s) {
     (void)hipSetDevice(s.device);
     void *bufs[] = {s.left, s.right, s.lut, s.lab_l, s.lab_r, s.wvl, s.wvr, s.whl, s.whr, s.c0, s.c1, s.den_v,
                     s.den_h, s.key, s.key_g, s.tkey, s.tkey_g, s.m1, s.m2, s.t1, s.t2, s.m2_g, s.t2_g, s.ref_l,
-                    s.ref_r, s.nb};
+                    s.ref_r, s.nb, s.cen_l, s.cen_r};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (s.comm) (void)ncclCommDestroy(s.comm);
@@ -438,9 +443,21 @@ int shard_aggregate(asw_ctx *c, int i, const uint8_t *left_rgba, const uint8_t *
         HIPCHK(hipMemcpyAsync(s.right, right_rgba, S * 4, hipMemcpyHostToDevice, st));
     }
     if (timed) HIPCHK(hipEventRecord(c->ev[e_raw], st));
-    // the raw cost (uint16 where the first pass reads it so)
-    if (s.raw16) ASWCHK(asw_raw_cost16(p, s.left, s.right, reinterpret_cast<uint16_t *>(s.c0), st));
-    else ASWCHK(asw_raw_cost(p, s.left, s.right, s.c0, st));
+    // the raw cost (uint16 where the first pass reads it so); census on: the transform of
+    // both images (d-independent, repeated by every shard) and the census cost in its place
+    const bool raw16 = c->census_on ? s.census16 : s.raw16;
+    if (c->census_on) {
+        ASWCHK(asw_census(p, &c->cen, s.left, s.cen_l, st));
+        ASWCHK(asw_census(p, &c->cen, s.right, s.cen_r, st));
+        if (raw16)
+            ASWCHK(asw_census_cost16(p, &c->cen, s.left, s.right, s.cen_l, s.cen_r, reinterpret_cast<uint16_t *>(s.c0),
+                                     st));
+        else ASWCHK(asw_census_cost(p, &c->cen, s.left, s.right, s.cen_l, s.cen_r, s.c0, st));
+    } else if (raw16) {
+        ASWCHK(asw_raw_cost16(p, s.left, s.right, reinterpret_cast<uint16_t *>(s.c0), st));
+    } else {
+        ASWCHK(asw_raw_cost(p, s.left, s.right, s.c0, st));
+    }
     if (timed) HIPCHK(hipEventRecord(c->ev[e_raw + 1], st));
     if (p->color_space == ASW_COLOR_LAB) {
         ASWCHK(asw_lab(p, s.left, s.lab_l, st));
@@ -457,7 +474,7 @@ int shard_aggregate(asw_ctx *c, int i, const uint8_t *left_rgba, const uint8_t *
     for (int it = 0; it < p->iters; ++it) {
         const int dmv = !s.den_v ? ASW_DEN_NONE : (it == 0 ? ASW_DEN_WRITE : ASW_DEN_READ);
         const int dm = !s.den_h ? ASW_DEN_NONE : (it == 0 ? ASW_DEN_WRITE : ASW_DEN_READ);
-        if (it == 0 && s.raw16)
+        if (it == 0 && raw16)
             ASWCHK(asw_aggregate_pass_den16(p, s.wvl, s.wvr, reinterpret_cast<const uint16_t *>(s.c0), s.c1, s.den_v,
                                             dmv, st));
         else ASWCHK(asw_aggregate_pass_den(p, ASW_DIR_V, s.wvl, s.wvr, s.c0, s.c1, s.den_v, dmv, st));
@@ -1020,6 +1037,30 @@ int asw_set_cross(asw_ctx *c, const asw_cross_params *cp, const asw_cross_output
     c->cp = *cp;
     c->cro = *o;
     c->cross_on = true;
+    return ASW_OK;
+}
+
+int asw_set_census(asw_ctx *c, const asw_census_params *cp) {
+    if (!c) return ASW_E_INVALID;
+    if (cp) {
+        for (int i = 0; i < c->n; ++i) ASWCHK(asw_census_params_check(&c->sh[i].p, cp));
+        for (int i = 0; i < c->n; ++i) {
+            Shard &s = c->sh[i];
+            HIPCHK(hipSetDevice(s.device));
+            if (!s.cen_l) ASWCHK(dev_alloc(&s.cen_l, asw_census_bytes(&s.p)));
+            if (!s.cen_r) ASWCHK(dev_alloc(&s.cen_r, asw_census_bytes(&s.p)));
+            s.census16 = !(s.p.flags & ASW_FLAG_RAW_F32) && asw_census16_supported(&s.p, cp);
+        }
+        HIPCHK(hipSetDevice(c->sh[0].device));
+        c->cen = *cp;
+    }
+    c->census_on = cp != nullptr;
+    if (c->gx_main) {  // the captured frame holds the previous cost's launches: capture again
+        (void)hipGraphExecDestroy(c->gx_main);
+        (void)hipGraphDestroy(c->g_main);
+        c->gx_main = nullptr;
+        c->g_main = nullptr;
+    }
     return ASW_OK;
 }
 

@@ -735,7 +735,9 @@ int asw_aggregate_pass_den16(const asw_params *p, const float *wvl, const float 
     if (!wvl || !wvr || !cin16 || !cout || (const void *)cin16 == (const void *)cout) return ASW_E_INVALID;
     if (den_mode != ASW_DEN_NONE && den_mode != ASW_DEN_WRITE) return ASW_E_INVALID;  // a first pass
     if (den_mode != ASW_DEN_NONE && (!den || den == cout)) return ASW_E_INVALID;
-    if (!asw_raw16_supported(p)) return ASW_E_UNSUPPORTED;
+    // a ring-kernel first pass; it never reads tad_tau (the volume may be asw_raw_cost16's or
+    // asw_census_cost16's, whose w_a = 0 form takes any tau)
+    if (p->iters < 1 || !asw::ring_taps(p->taps)) return ASW_E_UNSUPPORTED;
     const asw::RawSrc raw{cin16};
     return asw::launch_pass(p, ASW_DIR_V, wvl, wvr, nullptr, cout, den, den_mode, (hipStream_t)stream, &raw);
 }

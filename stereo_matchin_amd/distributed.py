@@ -129,14 +129,16 @@ class HipShardOps:
 
 
 class ShardedStereoMatcher:
-    """One rank's share of a d-sharded frame."""
+    """One rank's share of a d-sharded frame.  ``census``: as :class:`StereoMatcher`'s (each
+    rank repeats the d-independent transform and computes its own planes; ranks must
+    switch it alike)."""
 
-    def __init__(self, params: AswParams, rank: int, world: int, device="cuda", group=None):
+    def __init__(self, params: AswParams, rank: int, world: int, device="cuda", group=None, census=None):
         p = params.copy()
         p.d_begin, p.d_end = shard_range(params.ndisp, rank, world)
         self.p = p
         self.rank, self.world = rank, world
-        self.matcher = StereoMatcher(p, device)
+        self.matcher = StereoMatcher(p, device, census=census)
         self.ops = HipShardOps(p)
         self.reduce_min = _allreduce_min_factory(group)
 
@@ -196,7 +198,7 @@ class PipelinedMatcher:
     a caller that needs the volume (e.g. for ``refine``) copies it before then."""
 
     def __init__(self, params: AswParams, rank: int = 0, world: int = 1, device="cuda", group=None, depth: int = 2,
-                 overlap_prep: bool = False):
+                 overlap_prep: bool = False, census=None):
         self.device = torch.device(device)
         # overlap_prep: frame k+1's raw cost and support weights (d-independent of frame
         # k's volumes, in the other set's buffers) run on a third stream while frame k's
@@ -207,10 +209,10 @@ class PipelinedMatcher:
         self.prep = torch.cuda.Stream(self.device) if overlap_prep else None
         self.sharded = world > 1
         if self.sharded:
-            self.sets = [ShardedStereoMatcher(params, rank, world, self.device, group) for _ in range(depth)]
+            self.sets = [ShardedStereoMatcher(params, rank, world, self.device, group, census=census) for _ in range(depth)]
             self.p = self.sets[0].p
         else:
-            self.sets = [StereoMatcher(params, self.device) for _ in range(depth)]
+            self.sets = [StereoMatcher(params, self.device, census=census) for _ in range(depth)]
             self.p = self.sets[0].p
         self.side = torch.cuda.Stream(self.device)
         self.done: list = [None] * depth

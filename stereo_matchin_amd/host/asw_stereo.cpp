@@ -35,7 +35,11 @@
 //     cross_based_disparity.png and median.png; its timing columns (main.cpp:394-411)
 //     then stand in front of the ASW columns of every TSV row, after the id and followed by
 //     two empty columns, as in the reference's files.  Without --cross the files and the
-//     TSV are unchanged.
+//     TSV are unchanged;
+//   * --census replaces the AD raw cost by the census / AD-census cost (asw_set_census;
+//     --census-win WxH, --census-weights A,C: w_a * min(AD, tau) + w_c * hamming, A = 0 is
+//     census only).  The outputs and the TSV columns are unchanged; the `aggr` column then
+//     holds the time of the two transforms and the census cost.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -60,6 +64,8 @@ struct Options {
     bool lab = false, lr = true, native_lr = false, png16 = false, subpixel = false;
     bool cross = false;  // --cross: the cross-based matcher first (main.cpp:243-411)
     int cross_arm = -1, cross_tau = -1;
+    bool census = false;  // --census: the census / AD-census cost (asw_set_census)
+    int census_w = -1, census_h = -1, census_ad = -1, census_wc = -1;
 };
 
 void usage() {
@@ -68,6 +74,10 @@ void usage() {
                  "                  [--gamma-c G] [--gamma-g G] [--tau TAU] [--lab] [--no-lr] [--native-lr]\n"
                  "                  [--refine K] [--device I | --devices I,J,...] [--png16] [--tsv FILE]\n"
                  "                  [--subpixel] [--cross [--cross-arm N] [--cross-tau N]]\n"
+                 "                  [--census [--census-win WxH] [--census-weights A,C]]\n"
+                 "  --census    the census / AD-census cost A * min(AD, tau) + C * hamming in place of the AD raw cost\n"
+                 "              (robust to a gain / offset between the views); window W, H in 3, 5, 7, 9 but 9x9\n"
+                 "              (default 9x7), weights A 0..64, C 1..1024 (default 1,8; A = 0: census only)\n"
                  "  --cross     the reference's cross-based matcher first (one GPU, --ndisp <= 256): cross_based_initial.png,\n"
                  "              cross_based_disparity.png, median.png, and its timing columns in front of the ASW columns of the TSV\n"
                  "  --subpixel  float sub-pixel disparity (needs --ndisp <= 1024): asw_disparity_sub.pfm (LR-masked,\n"
@@ -113,6 +123,17 @@ bool parse(int argc, char **argv, Options &o) {
         else if (a == "--cross") o.cross = true;
         else if (a == "--cross-arm") { if (!(v = next("--cross-arm"))) return false; o.cross_arm = std::atoi(v); }
         else if (a == "--cross-tau") { if (!(v = next("--cross-tau"))) return false; o.cross_tau = std::atoi(v); }
+        else if (a == "--census") o.census = true;
+        else if (a == "--census-win") {
+            if (!(v = next("--census-win"))) return false;
+            if (std::sscanf(v, "%dx%d", &o.census_w, &o.census_h) != 2) return false;
+            o.census = true;
+        }
+        else if (a == "--census-weights") {
+            if (!(v = next("--census-weights"))) return false;
+            if (std::sscanf(v, "%d,%d", &o.census_ad, &o.census_wc) != 2) return false;
+            o.census = true;
+        }
         else if (a == "--lab") o.lab = true;
         else if (a == "--no-lr") o.lr = false;
         else if (a == "--native-lr") o.native_lr = true;
@@ -232,6 +253,19 @@ int main(int argc, char **argv) {
             st = asw_set_refine(ctx, &rp);
             if (st != ASW_OK) {
                 std::fprintf(stderr, "%s: asw_set_refine: %s\n", folder.c_str(), asw_strerror(st));
+                ++failures;
+                asw_destroy(ctx);
+                continue;
+            }
+        }
+        if (o.census) {
+            asw_census_params np;
+            asw_census_params_default(&np);
+            if (o.census_w >= 0) np.win_w = o.census_w, np.win_h = o.census_h;
+            if (o.census_ad >= 0) np.ad_weight = o.census_ad, np.census_weight = o.census_wc;
+            st = asw_set_census(ctx, &np);
+            if (st != ASW_OK) {
+                std::fprintf(stderr, "%s: asw_set_census: %s\n", folder.c_str(), asw_strerror(st));
                 ++failures;
                 asw_destroy(ctx);
                 continue;

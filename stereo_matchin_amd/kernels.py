@@ -128,6 +128,50 @@ def asw_vCostAggregation16(p: AswParams, supp_left, supp_right, cost16, out=None
     return out
 
 
+# ------------------------------------------------------- census / AD-census cost
+# No reference counterpart (its only raw cost is the RGB AD): include/asw.h §census.
+
+def census(p: AswParams, cp, img: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """asw_census: the census codes of an RGBA8 image, uint64 bit patterns in int64 [H][W]."""
+    _expect(img, (p.height, p.width, 4), torch.uint8, "img")
+    if out is None:
+        out = torch.empty((p.height, p.width), dtype=torch.int64, device=img.device)
+    _expect(out, (p.height, p.width), torch.int64, "out")
+    _lib.check(_lib.lib().asw_census(ctypes.byref(p), ctypes.byref(cp), _ptr(img), _ptr(out), _stream(img.device)),
+               "asw_census")
+    return out
+
+
+def _census_cost(name: str, dtype, p, cp, left, right, cen_left, cen_right, out):
+    for img in (left, right):
+        _expect(img, (p.height, p.width, 4), torch.uint8, "image")
+    for cen in (cen_left, cen_right):
+        _expect(cen, (p.height, p.width), torch.int64, "census")
+    if out is None:
+        out = torch.empty(cost_shape(p), dtype=dtype, device=left.device)
+    _expect(out, cost_shape(p), dtype, "out")
+    _lib.check(getattr(_lib.lib(), name)(ctypes.byref(p), ctypes.byref(cp), _ptr(left), _ptr(right), _ptr(cen_left),
+                                         _ptr(cen_right), _ptr(out), _stream(left.device)), name)
+    return out
+
+
+def census_cost(p: AswParams, cp, left, right, cen_left, cen_right, out: torch.Tensor | None = None):
+    """asw_census_cost: ``min(AD, tau) * w_a + w_c * hamming`` for planes [d_begin, d_end),
+    float32 [H][W][Dp]."""
+    return _census_cost("asw_census_cost", torch.float32, p, cp, left, right, cen_left, cen_right, out)
+
+
+def census_cost16(p: AswParams, cp, left, right, cen_left, cen_right, out: torch.Tensor | None = None):
+    """asw_census_cost16: the same costs as uint16 (integers <= 65535) in int16 storage
+    [H][W][Dp], what asw_vCostAggregation16 reads."""
+    return _census_cost("asw_census_cost16", torch.int16, p, cp, left, right, cen_left, cen_right, out)
+
+
+def census16_supported(p: AswParams, cp) -> bool:
+    """asw_census16_supported: asw_census_cost16 and the first V pass over it are built."""
+    return bool(_lib.lib().asw_census16_supported(ctypes.byref(p), ctypes.byref(cp)))
+
+
 def support_lut(p: AswParams, device, out: torch.Tensor | None = None) -> torch.Tensor:
     """(R+1) x 766 table of exp(-sad/gamma_c - dist/gamma_g) (K/asw_vsupport.cl:22-25)."""
     if out is None:

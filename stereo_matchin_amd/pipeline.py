@@ -50,13 +50,21 @@ class StereoMatcher:
 
     ``den_cache`` (default on for r >= 2): keep the two aggregation denominators
     (V, H) as volumes — written by the first pass of each direction, read by the
-    other r-1 (ASW_DEN_*); bit-identical results, 2 more cost-sized buffers."""
+    other r-1 (ASW_DEN_*); bit-identical results, 2 more cost-sized buffers.
 
-    def __init__(self, params: AswParams, device="cuda", den_cache: bool = True):
+    ``census``: None (the AD raw cost), True (the default AD-census cost) or an
+    AswCensusParams: ``raw_and_support`` then runs asw_census on both images and the census
+    cost in place of asw_Aggr (include/asw.h §census)."""
+
+    def __init__(self, params: AswParams, device="cuda", den_cache: bool = True, census=None):
         st = _lib.params_check(params)
         if st != _lib.ASW_OK:
             raise _lib.AswError(st, "asw_params_check")
         self.p = params.copy()
+        self.census = _lib.census_params_of(census)
+        if self.census is not None:
+            _lib.check(_lib.lib().asw_census_params_check(ctypes.byref(self.p), ctypes.byref(self.census)),
+                       "asw_census_params_check")
         self.device = torch.device(device)
         dev = self.device
         self.lut = torch.empty(K.lut_shape(self.p), dtype=torch.float32, device=dev)
@@ -66,7 +74,12 @@ class StereoMatcher:
         # the raw costs as uint16 in c0's first half (asw_raw_cost16 + the first V pass
         # asw_aggregate_pass_den16: half the bytes of asw_Aggr's write and that pass's read,
         # bit-identical); ASW_FLAG_RAW_F32 keeps the float volume
-        self.raw16 = not params.flags & _lib.FLAG_RAW_F32 and K.raw16_supported(self.p)
+        self.raw16 = not params.flags & _lib.FLAG_RAW_F32 and (
+            K.raw16_supported(self.p) if self.census is None else K.census16_supported(self.p, self.census))
+        self.cen_l = self.cen_r = None
+        if self.census is not None:
+            self.cen_l = torch.empty((self.p.height, self.p.width), dtype=torch.int64, device=dev)
+            self.cen_r = torch.empty_like(self.cen_l)
         self.c0_16 = K.cost16_view(self.c0) if self.raw16 else None
         self.den_v = self.den_h = None
         if den_cache and self.p.iters >= 2 and K.cost_shape(self.p)[2] != 32:
@@ -81,9 +94,17 @@ class StereoMatcher:
 
     # -- stages ---------------------------------------------------------------
     def raw_and_support(self, left: torch.Tensor, right: torch.Tensor):
-        """asw_Aggr into c0 and the four support arrays."""
+        """asw_Aggr (or the census cost) into c0 and the four support arrays."""
         p = self.p
-        if self.raw16:
+        if self.census is not None:
+            cp = self.census
+            K.census(p, cp, left, out=self.cen_l)
+            K.census(p, cp, right, out=self.cen_r)
+            if self.raw16:
+                K.census_cost16(p, cp, left, right, self.cen_l, self.cen_r, out=self.c0_16)
+            else:
+                K.census_cost(p, cp, left, right, self.cen_l, self.cen_r, out=self.c0)
+        elif self.raw16:
             K.asw_Aggr16(p, left, right, out=self.c0_16)
         else:
             K.asw_Aggr(p, left, right, out=self.c0)
@@ -236,7 +257,7 @@ class FrameContext:
     """
 
     def __init__(self, params: AswParams, devices=(0,), rank: int | None = None, nranks: int | None = None,
-                 comm_id: bytes | None = None, refine=None, graph: bool = False):
+                 comm_id: bytes | None = None, refine=None, graph: bool = False, census=None):
         self.L = _lib.lib()
         self.p = params.copy()
         self.ctx = ctypes.c_void_p()
@@ -258,6 +279,18 @@ class FrameContext:
             _lib.check(self.L.asw_set_refine(self.ctx, ctypes.byref(refine)), "asw_set_refine")
         if graph:  # asw_set_graph: capture the device work into HIP graphs, replay them
             _lib.check(self.L.asw_set_graph(self.ctx, 1), "asw_set_graph")
+        self.census = None
+        if census is not None and census is not False:
+            self.set_census(census)
+
+    def set_census(self, census=True) -> None:
+        """``asw_set_census``: the census / AD-census cost in place of the AD raw cost of every
+        later match.  ``census``: an AswCensusParams, True for the defaults (9 x 7, AD + 8 x
+        census), None / False to turn it off again.  Ranks of a multi-process frame must
+        switch it alike."""
+        cp = _lib.census_params_of(census)
+        _lib.check(self.L.asw_set_census(self.ctx, ctypes.byref(cp) if cp is not None else None), "asw_set_census")
+        self.census = cp
 
     def set_cross(self, cross_params=True, timings: bool = True) -> None:
         """``asw_set_cross``: run the cross-based matcher (main.cpp:243-411) ahead of the ASW
@@ -387,7 +420,8 @@ def comm_unique_id() -> bytes:
 
 
 def match_frame(params: AswParams, left_rgba: np.ndarray, right_rgba: np.ndarray, device: int = 0,
-                want_cost: bool = False, refine=None, devices=None, want16: bool = False) -> dict:
+                want_cost: bool = False, refine=None, devices=None, want16: bool = False, census=None) -> dict:
     """Frame API (``asw_create`` + ``asw_match``): host RGBA8 in, host maps out."""
-    with FrameContext(params, devices=devices if devices is not None else (device,), refine=refine) as fc:
+    with FrameContext(params, devices=devices if devices is not None else (device,), refine=refine,
+                      census=census) as fc:
         return fc.match(left_rgba, right_rgba, want_cost=want_cost, want16=want16)
