@@ -516,6 +516,13 @@ static void wta_ref(const float *C, const float *ref, const float *ref_t, int W,
         }
 }
 
+/* asw_WTA_REF alone on a caller's volume C [D][H][W] and estimates ref / ref_t
+ * ([2][H][W]: value plane, den plane): the function oracle_refine calls. */
+void oracle_wta_ref(const float *C, const float *ref, const float *ref_t, int W, int H, int D, int pol,
+                    int32_t *d_ref, int32_t *d_tar, float *conf_ref) {
+    wta_ref(C, ref, ref_t, W, H, D, pol, d_ref, d_tar, conf_ref);
+}
+
 /* 3x3 median of a u8 code image with clamped borders (K/median.cl: the
  * min/max network yields the exact median of the 9 samples per channel). */
 static void median3(const uint8_t *in, int W, int H, uint8_t *out) {

@@ -42,8 +42,11 @@ def _host_has_v3() -> bool:
 
 def build(force: bool = False) -> None:
     """Compile the oracle shared objects with the committed Makefile."""
-    need = force or not (os.path.exists(os.path.join(_HERE, "liboracle.so"))
-                         and os.path.exists(os.path.join(_HERE, "liboracle_v3.so")))
+    libs = [os.path.join(_HERE, n) for n in ("liboracle.so", "liboracle_v3.so")]
+    need = force or not all(os.path.exists(so) for so in libs)
+    if not need:  # a library left by an older asw_oracle.c lacks the newer entry points
+        src = os.path.getmtime(os.path.join(_HERE, "asw_oracle.c"))
+        need = any(os.path.getmtime(so) < src for so in libs)
     if need:
         subprocess.check_call(["make", "-s", "-C", _HERE, "all"])
 
@@ -82,6 +85,8 @@ def lib():
     L.oracle_lab.argtypes = [P, i, i, P]
     L.oracle_refine.argtypes = [P, P, i, i, i, i, i, i, P, P, P, P, P, P, P, P, P]
     L.oracle_refine.restype = i
+    L.oracle_wta_ref.argtypes = [P, P, P, i, i, i, i, P, P, P]
+    L.oracle_wta_ref.restype = None
     L.oracle_support_lab.argtypes = [P, i, i, i, i, f, f, P]
     _lib = L
     return L
@@ -155,6 +160,20 @@ def wta(C: np.ndarray):
     ct = np.empty((H, W), np.float32)
     lib().oracle_wta(_p(C), W, H, D, _p(dr), _p(cr), _p(dt), _p(ct))
     return dr, cr, dt, ct
+
+
+def wta_ref(C: np.ndarray, ref_l: np.ndarray, ref_r: np.ndarray, pol: int = REF_POL):
+    """asw_WTA_REF (K/asw_wta_ref.cl:2-68) on a volume [D][H][W] and the two views'
+    estimates [2][H][W] (value plane, den plane): ``(d_ref, d_tar, conf_ref)``, conf_ref
+    being the TARGET confidence as in the reference."""
+    D, H, W = C.shape
+    assert ref_l.shape == (2, H, W) and ref_r.shape == (2, H, W)
+    assert C.dtype == ref_l.dtype == ref_r.dtype == np.float32
+    dr = np.empty((H, W), np.int32)
+    dt = np.empty((H, W), np.int32)
+    cr = np.empty((H, W), np.float32)
+    lib().oracle_wta_ref(_p(C), _p(ref_l), _p(ref_r), W, H, D, pol, _p(dr), _p(dt), _p(cr))
+    return dr, dt, cr
 
 
 def code_u8(d, D: int):

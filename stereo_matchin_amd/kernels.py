@@ -554,6 +554,56 @@ def asw_WTA_REF(p: AswParams, cost: torch.Tensor, ref_l: torch.Tensor, ref_r: to
     return d_ref, d_tar, code_ref, code_tar
 
 
+# d-sharded asw_WTA_REF (include/asw.h): the wta_local protocol on the penalised values,
+# ref_l / ref_r = asw_ref_h's [2][H][W] output of each view.
+
+def wta_ref_local(p: AswParams, cost, ref_l):
+    H, W = p.height, p.width
+    dev = cost.device
+    _expect(cost, cost_shape(p), torch.float32, "cost")
+    _expect(ref_l, (2, H, W), torch.float32, "ref_l")
+    key = torch.empty((H, W), dtype=torch.int64, device=dev)
+    m1 = torch.empty((H, W), dtype=torch.float32, device=dev)
+    m2 = torch.empty_like(m1)
+    _lib.check(_lib.lib().asw_wta_ref_local(ctypes.byref(p), _ptr(cost), _ptr(ref_l), _ptr(key), _ptr(m1), _ptr(m2),
+                                            _stream(dev)), "asw_wta_ref_local")
+    return key, m1, m2
+
+
+def wta_ref_target_local(p: AswParams, cost, ref_r, key_ref):
+    H, W = p.height, p.width
+    dev = cost.device
+    _expect(cost, cost_shape(p), torch.float32, "cost")
+    _expect(ref_r, (2, H, W), torch.float32, "ref_r")
+    _expect(key_ref, (H, W), torch.int64, "key_ref")
+    tkey = torch.empty((H, W), dtype=torch.int64, device=dev)
+    t1 = torch.empty((H, W), dtype=torch.float32, device=dev)
+    t2 = torch.empty_like(t1)
+    _lib.check(_lib.lib().asw_wta_ref_target_local(ctypes.byref(p), _ptr(cost), _ptr(ref_r), _ptr(key_ref),
+                                                   _ptr(tkey), _ptr(t1), _ptr(t2), _stream(dev)),
+               "asw_wta_ref_target_local")
+    return tkey, t1, t2
+
+
+def wta_ref_finalize(p: AswParams, key, tkey, t2):
+    """Returns ``(d_ref, d_tar, conf_ref, code_ref, code_tar)``; conf_ref is the TARGET
+    confidence, as :func:`asw_WTA_REF` writes it."""
+    H, W = p.height, p.width
+    dev = key.device
+    _expect(key, (H, W), torch.int64, "key")
+    _expect(tkey, (H, W), torch.int64, "tkey")
+    _expect(t2, (H, W), torch.float32, "t2")
+    d_ref = torch.empty((H, W), dtype=torch.int32, device=dev)
+    d_tar = torch.empty_like(d_ref)
+    conf_ref = torch.empty((H, W), dtype=torch.float32, device=dev)
+    code_ref = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    code_tar = torch.empty_like(code_ref)
+    _lib.check(_lib.lib().asw_wta_ref_finalize(ctypes.byref(p), _ptr(key), _ptr(tkey), _ptr(t2), _ptr(d_ref),
+                                               _ptr(d_tar), _ptr(conf_ref), _ptr(code_ref), _ptr(code_tar),
+                                               _stream(dev)), "asw_wta_ref_finalize")
+    return d_ref, d_tar, conf_ref, code_ref, code_tar
+
+
 def Median(p: AswParams, codes: torch.Tensor) -> torch.Tensor:
     """3x3 median (K/median.cl:58-88) of u8 codes [H][W] or of channel 0 of RGBA8 [H][W][4]."""
     stride = 4 if codes.dim() == 3 else 1

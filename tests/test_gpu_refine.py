@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, load_scene, pixel_major
+from wta_shard_ref import case_seed, refine_estimates, well_volume
 
 pytestmark = pytest.mark.gpu
 
@@ -128,21 +129,51 @@ def test_frame_api_refine(gpu, oracle):
     assert out["timings"]["refine"] > 0
 
 
-@pytest.mark.parametrize("variant", [0, 2])
-@pytest.mark.parametrize("H,W,D", [(1, 1, 1), (5, 67, 61), (13, 129, 256), (3, 200, 300), (7, 64, 33),
-                                   (2, 700, 128), (4, 1000, 256), (3, 63, 200), (2, 300, 2)])
-def test_wta_variants_on_random_volume(gpu, oracle, variant, H, W, D):
+_WTA_SHAPES = [(1, 1, 1), (5, 67, 61), (13, 129, 256), (3, 200, 300), (7, 64, 33), (2, 700, 128), (4, 1000, 256),
+               (3, 63, 200), (2, 300, 2)]
+_wta_inputs = {}
+
+
+def _wta_input(oracle, kind, H, W, D):
+    """(cost [D][H][W], oracle.wta of it), computed once per (kind, shape) and read only."""
+    if (kind, H, W, D) not in _wta_inputs:
+        if kind == "levels":
+            rng = np.random.default_rng(H * W + D)
+            cost = rng.integers(1, 9, (D, H, W)).astype(np.float32)  # small integers: ties everywhere
+        else:
+            cost = well_volume(D, H, W, case_seed(D, H, W))
+        _wta_inputs[kind, H, W, D] = cost, oracle.wta(cost)
+    return _wta_inputs[kind, H, W, D]
+
+
+@pytest.mark.parametrize("variant,H,W,D,kind", [
+    pytest.param(v, H, W, D, kind, id=f"{H}-{W}-{D}-{v}" + ("" if kind == "levels" else f"-{kind}"))
+    for kind in ("levels", "wells") for H, W, D in _WTA_SHAPES for v in (0, 2)])
+def test_wta_variants_on_random_volume(gpu, oracle, variant, H, W, D, kind):
     """asw_WTA: the lane-per-pixel scan (variant 0) and the row sweep (2: Dp 64 / 128 /
     256, the scan elsewhere; round 1's wave-per-pixel form is checked by
-    tools/exp/exp_forms.py) against the oracle on
-    volumes with many exact ties (rows longer than the 255-plane diagonals, the clamped
-    first points of pixels x < md, rows not a multiple of 64 pixels)."""
+    tools/exp/exp_forms.py) against the oracle, on two kinds of volume.
+
+    `levels` draws every voxel from eight values: ties everywhere, rows not a multiple of
+    64 pixels.  It checks the own scan's first-argmin and second-minimum rules; its d_ref
+    is the first occurrence of the lowest level (a small index) and no diagonal neighbour
+    is strictly lower, so its target scan never moves d_tar off d_ref.
+
+    `wells` (wta_shard_ref.well_volume) puts each pixel's minimum at a plane drawn over
+    the whole range and lets diagonal neighbours be lower: the target scan decides d_tar,
+    over rows longer than the 255-plane diagonals and, for the pixels x < d_ref, through
+    its clamped steps.  Where W and D are at least 100 the test first asserts that: d_tar
+    != d_ref at a quarter of the pixels or more, and d_ref > x at 0.30 * min(1, D / W) of
+    them (d_ref < D, so at most D / W of a row can have it; the recipe gives about half of
+    min(1, D / W) or more, the bound asks for 0.3 of it)."""
     import stereo_matchin_amd.kernels as K
     from stereo_matchin_amd import _lib
-    rng = np.random.default_rng(H * W + D)
-    cost = rng.integers(1, 9, (D, H, W)).astype(np.float32)  # small integers: ties everywhere
+    cost, want = _wta_input(oracle, kind, H, W, D)
+    if kind == "wells" and W >= 100 and D >= 100:
+        moved, clamped = np.mean(want[2] != want[0]), np.mean(want[0] > np.arange(W))
+        print(f"wells {H}x{W}x{D}: d_tar != d_ref {moved:.3f}, d_ref > x {clamped:.3f}")
+        assert moved >= 0.25 and clamped >= 0.30 * min(1.0, D / W), (moved, clamped)
     p = _params(W, H, D, 3)
-    want = oracle.wta(cost)
     old = _lib.lib().asw_tune_set(2, variant)
     try:
         got = K.asw_WTA(p, _t(pixel_major(cost, K.cost_shape(p)[2]), gpu))
@@ -150,3 +181,30 @@ def test_wta_variants_on_random_volume(gpu, oracle, variant, H, W, D):
         _lib.lib().asw_tune_set(2, old)
     for i, (g, w) in enumerate(zip(got[:4], want[:4])):
         assert np.array_equal(_np(g), w), (i, np.argwhere(_np(g) != w)[:5])
+
+
+@pytest.mark.parametrize("D,H,W", [(61, 5, 67), (256, 13, 129)])
+def test_wta_ref_on_well_volume(gpu, oracle, D, H, W):
+    """asw_WTA_REF alone on a crafted volume and crafted estimates (den = 0: the ties of
+    the plain scan; den = 3e7: nothing below the sentinel) against oracle.wta_ref; the
+    loop tests above reach it only with the estimates of natural images."""
+    import torch
+
+    import stereo_matchin_amd.kernels as K
+    seed = case_seed(D, H, W)
+    C = well_volume(D, H, W, seed)
+    ref_l, ref_r = refine_estimates(H, W, D, seed + 1)
+    want = oracle.wta_ref(C, ref_l, ref_r)
+    if W >= 100:
+        moved, clamped = np.mean(want[1] != want[0]), np.mean(want[0] > np.arange(W))
+        print(f"wells+estimates {H}x{W}x{D}: d_tar != d_ref {moved:.3f}, d_ref > x {clamped:.3f}")
+        assert moved >= 0.25 and clamped >= 0.30, (moved, clamped)
+    p = _params(W, H, D, 3)
+    conf = torch.full((H, W), -1.0, dtype=torch.float32, device=gpu)  # written in place
+    d_ref, d_tar, code_ref, code_tar = K.asw_WTA_REF(p, _t(pixel_major(C, K.cost_shape(p)[2]), gpu), _t(ref_l, gpu),
+                                                     _t(ref_r, gpu), conf)
+    for name, g, w in zip(("d_ref", "d_tar", "conf_ref", "code_ref", "code_tar"),
+                          (d_ref, d_tar, conf, code_ref, code_tar),
+                          want + (oracle.code_u8(want[0], D), oracle.code_u8(want[1], D))):
+        assert _np(g).dtype == w.dtype and np.array_equal(_np(g), w, equal_nan=w.dtype.kind == "f"), \
+            (name, np.argwhere(_np(g) != w)[:5])

@@ -1,0 +1,165 @@
+"""The d-sharded WTA stage kernels (k_wta_local_scan, k_wta_target_local_scan, k_wta_second,
+k_wta_finalize, k_wta_ref_finalize: asw_wta_local & co. and the penalised asw_wta_ref_*
+forms of include/asw.h) on an MI355X, stage by stage and shard by shard against the numpy
+restatement of tests/wta_shard_ref.py (pinned to the C oracle in test_wta_shard_ref.py),
+then combined against oracle.wta / oracle.wta_ref and the unsharded kernels.  Bit for bit.
+
+The volumes are well_volume's: the minimum tied within and across shards, a target scan
+that leaves d_ref (often into another shard, mostly through its clamped part d_ref > x),
+pixels with nothing below the sentinel, zero padding planes below every real value.  The
+cases with W >= 100 and 3 or more shards assert those properties before they compare.
+"""
+import functools
+
+import numpy as np
+import pytest
+
+from conftest import pixel_major
+from wta_shard_ref import CASES, case_id, case_seed, shard_case, well_volume
+
+pytestmark = pytest.mark.gpu
+
+
+def _t(a, dev):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def _np(t):
+    return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+
+
+def _same(got, want, what):
+    g, w = _np(got), _np(want)
+    assert g.dtype == w.dtype and g.shape == w.shape, (what, g.dtype, w.dtype, g.shape, w.shape)
+    assert np.array_equal(g, w, equal_nan=g.dtype.kind == "f"), (what, np.argwhere(g != w)[:5].tolist())
+
+
+def _same_all(got, want, kernel, names, shard=None):
+    for n, g, w in zip(names, got, want):
+        _same(g, w, f"{kernel} {n}" + ("" if shard is None else f", shard {shard}"))
+
+
+def _min(ts):
+    import torch
+    return functools.reduce(torch.minimum, ts)
+
+
+def _params(W, H, D, **kw):
+    from stereo_matchin_amd import make_params
+    return make_params(W, H, ndisp=D, taps=3, iters=1, **kw)
+
+
+def _device_case(c, gpu):
+    """(per-shard params, per-shard device volumes [H][W][Dp] with zero padding planes)."""
+    import stereo_matchin_amd.kernels as K
+    ps = [_params(c.W, c.H, c.D, d_begin=b, d_end=e) for b, e in c.spans]
+    costs = [_t(pixel_major(c.C[b:e], K.cost_shape(p)[2]), gpu) for p, (b, e) in zip(ps, c.spans)]
+    return ps, costs
+
+
+def _whole(c, gpu):
+    import stereo_matchin_amd.kernels as K
+    p = _params(c.W, c.H, c.D)
+    return p, _t(pixel_major(c.C, K.cost_shape(p)[2]), gpu)
+
+
+@pytest.mark.parametrize("case", CASES, ids=case_id)
+def test_plain_stages_and_result(gpu, oracle, case):
+    """asw_wta_local -> min -> asw_wta_second -> min -> asw_wta_target_local -> min ->
+    asw_wta_second -> min -> asw_wta_finalize, each stage of each shard against CpuShardOps,
+    the result against oracle.wta and asw_WTA on the unsharded device volume."""
+    import stereo_matchin_amd.kernels as K
+    c = shard_case(*case)
+    c.assert_conditions()
+    ps, costs = _device_case(c, gpu)
+    n = range(len(ps))
+
+    loc = [K.wta_local(ps[s], costs[s]) for s in n]
+    for s in n:
+        _same_all(loc[s], c.local[s], "k_wta_local_scan", ("key", "m1", "m2"), s)
+    key_g = _min([k for k, _, _ in loc])
+    sec = [K.wta_second(ps[s], key_g, *loc[s]) for s in n]
+    for s in n:
+        _same(sec[s], c.second[s], f"k_wta_second (ref), shard {s}")
+    m2_g = _min(sec)
+
+    tar = [K.wta_target_local(ps[s], costs[s], key_g) for s in n]
+    for s in n:
+        _same_all(tar[s], c.target[s], "k_wta_target_local_scan", ("tkey", "t1", "t2"), s)
+    tkey_g = _min([k for k, _, _ in tar])
+    tsec = [K.wta_second(ps[s], tkey_g, *tar[s]) for s in n]
+    for s in n:
+        _same(tsec[s], c.tsecond[s], f"k_wta_second (tar), shard {s}")
+    t2_g = _min(tsec)
+
+    names = ("d_ref", "conf_ref", "d_tar", "conf_tar")
+    fin = K.wta_finalize(ps[0], key_g, m2_g, tkey_g, t2_g)
+    _same_all(fin[:4], c.final, "k_wta_finalize (restatement)", names)
+    want = oracle.wta(c.C)
+    _same_all(fin[:4], want, "k_wta_finalize (oracle)", names)
+    if c.D <= 256:
+        _same(fin[4], oracle.code_u8(want[0], c.D), "code_ref")
+        _same(fin[5], oracle.code_u8(want[2], c.D), "code_tar")
+    pw, whole = _whole(c, gpu)
+    _same_all(fin, K.asw_WTA(pw, whole), "asw_WTA (unsharded)", names + ("code_ref", "code_tar"))
+
+
+@pytest.mark.parametrize("case", CASES, ids=case_id)
+def test_penalised_stages_and_result(gpu, oracle, case):
+    """asw_wta_ref_local -> min -> asw_wta_ref_target_local -> min -> asw_wta_second -> min ->
+    asw_wta_ref_finalize against CpuRefShardOps, oracle.wta_ref and asw_WTA_REF."""
+    import torch
+
+    import stereo_matchin_amd.kernels as K
+    c = shard_case(*case)
+    c.assert_conditions()
+    ps, costs = _device_case(c, gpu)
+    ref_l, ref_r = _t(c.ref_l, gpu), _t(c.ref_r, gpu)
+    n = range(len(ps))
+
+    loc = [K.wta_ref_local(ps[s], costs[s], ref_l) for s in n]
+    for s in n:
+        _same_all(loc[s], c.rlocal[s], "k_wta_local_scan<PEN>", ("key", "m1", "m2"), s)
+    key_g = _min([k for k, _, _ in loc])
+    tar = [K.wta_ref_target_local(ps[s], costs[s], ref_r, key_g) for s in n]
+    for s in n:
+        _same_all(tar[s], c.rtarget[s], "k_wta_target_local_scan<PEN>", ("tkey", "t1", "t2"), s)
+    tkey_g = _min([k for k, _, _ in tar])
+    tsec = [K.wta_second(ps[s], tkey_g, *tar[s]) for s in n]
+    for s in n:
+        _same(tsec[s], c.rtsecond[s], f"k_wta_second (tar), shard {s}")
+    t2_g = _min(tsec)
+
+    names = ("d_ref", "d_tar", "conf_ref")
+    fin = K.wta_ref_finalize(ps[0], key_g, tkey_g, t2_g)
+    _same_all(fin[:3], c.rfinal, "k_wta_ref_finalize (restatement)", names)
+    want = oracle.wta_ref(c.C, c.ref_l, c.ref_r)
+    _same_all(fin[:3], want, "k_wta_ref_finalize (oracle)", names)
+    if c.D <= 256:
+        _same(fin[3], oracle.code_u8(want[0], c.D), "code_ref")
+        _same(fin[4], oracle.code_u8(want[1], c.D), "code_tar")
+    pw, whole = _whole(c, gpu)
+    conf = torch.full((c.H, c.W), -1.0, dtype=torch.float32, device=gpu)  # written in place
+    d_ref, d_tar, code_ref, code_tar = K.asw_WTA_REF(pw, whole, ref_l, ref_r, conf)
+    _same_all(fin, (d_ref, d_tar, conf, code_ref, code_tar), "asw_WTA_REF (unsharded)",
+              names + ("code_ref", "code_tar"))
+
+
+@pytest.mark.parametrize("D,H,W", [(61, 5, 67), (300, 3, 200)])
+def test_one_shard_from_local(gpu, oracle, D, H, W):
+    """K.wta_from_local, the one-shard case of the protocol (what the pipelined matcher
+    runs after the last pass's local scan), on the well volume."""
+    import stereo_matchin_amd.kernels as K
+    C = well_volume(D, H, W, case_seed(D, H, W))
+    want = oracle.wta(C)
+    x = np.arange(W)
+    if W >= 100:
+        assert np.mean(want[2] != want[0]) >= 0.25 and np.mean(want[0] > x) >= 0.30
+    p = _params(W, H, D)
+    cost = _t(pixel_major(C, K.cost_shape(p)[2]), gpu)
+    key, m1, m2 = K.wta_local(p, cost)
+    got = K.wta_from_local(p, cost, key, m1, m2)
+    names = ("d_ref", "conf_ref", "d_tar", "conf_tar")
+    _same_all(got[:4], want, "wta_from_local", names)
+    _same_all(got, K.asw_WTA(p, cost), "asw_WTA", names + ("code_ref", "code_tar"))
