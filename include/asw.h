@@ -97,7 +97,10 @@ int asw_last_hip_error(void); /* hipError_t of the last ASW_E_HIP */
  *      its own asw_subpixel_outputs struct; the cross-based matcher's entry points
  *      (asw_median3_rgba, asw_cross_*) and asw_set_cross with its own structs; the census /
  *      AD-census matching cost (asw_census_*, asw_census, asw_census_cost, asw_census_cost16,
- *      asw_census16_supported) and asw_set_census with its own asw_census_params struct. */
+ *      asw_census16_supported) and asw_set_census with its own asw_census_params struct; the
+ *      native refinement loop (asw_refine_native_*, asw_ref_v_native, asw_consistency_native,
+ *      asw_median3_u16, asw_refine_native) and asw_set_refine_native with its own
+ *      asw_refine_native_outputs struct. */
 #define ASW_ABI_VERSION 4
 int asw_abi_version(void);
 
@@ -329,7 +332,8 @@ int asw_refine_lut(const asw_params *p, const asw_refine_params *rp, float *lut,
  * plane 0 = the refined disparity estimate num/den, plane 1 = den. */
 int asw_ref_v(const asw_params *p, const asw_refine_params *rp, const uint8_t *img_rgba, const uint8_t *est,
               int est_stride, const float *conf, const float *lut, float *out, void *stream);
-/* replaces asw_ref_h (K/asw_refinement_h.cl:16-53), main.cpp:561-573; in/out [2][H][W]. */
+/* replaces asw_ref_h (K/asw_refinement_h.cl:16-53), main.cpp:561-573; in/out [2][H][W].
+ * It reads no disparity: also accepted where asw_refine_native_params_check passes. */
 int asw_ref_h(const asw_params *p, const asw_refine_params *rp, const uint8_t *img_rgba, const float *conf,
               const float *in, const float *lut, float *out, void *stream);
 /* replaces asw_WTA_REF (K/asw_wta_ref.cl:2-68), main.cpp:576-586: first-argmin of
@@ -354,6 +358,52 @@ int asw_refine(const asw_params *p, const asw_refine_params *rp, const uint8_t *
                const float *cost, uint8_t *est_left_rgba, uint8_t *code_tar, float *conf_ref, float *conf_tar,
                void *workspace, uint8_t *post_red_rgba, uint8_t *final_rgba, int32_t *d_ref, int32_t *d_tar,
                void *stream);
+
+/* ---- native refinement: the loop above on disparity INDICES (no reference counterpart:
+ * the reference feeds disparities back through 8-bit images, which collide above 256 levels).
+ * The estimates are int32 index maps, the outputs uint16 maps; any ndisp <= 65535, either
+ * lr_mode.  Every operation is an IEEE float32 one in the stated order, no contraction: the
+ * arithmetic of the 8-bit loop's kernels with the decode replaced (DESIGN.md §Native
+ * refinement).  Per iteration, for both views:
+ *   1. V estimate (asw_ref_v_native): asw_ref_v with Dv = (float)est[q] in place of
+ *      (code/255)*(ndisp-1): over the taps i = 0..taps-1, q = (x, clamp(y+i-R)),
+ *      t = w*conf[q]; num = num + t*Dv; den = den + t (num = den = 1e-5f on entry);
+ *      out [2][H][W] = num/den, den.  Left view: est = est_left; right view: est = d_tar.
+ *   2. H estimate: asw_ref_h, unchanged.
+ *   3. asw_wta_ref with NULL code outputs: d_ref, d_tar, conf_ref <- the target confidence.
+ *   4. asw_consistency_native: cons = |d_ref[p] - d_tar[p]| <= 1; where !cons both
+ *      confidences are set to 0; est_left[p] = cons ? d_ref[p] : d_tar[p] (K/consist.cl
+ *      writes the target value); post16[p] = cons ? d_ref[p] : ASW_DISP16_INVALID.
+ * After the last iteration final16 = asw_median3_u16(est_left): the 3x3 clamp-to-edge median.
+ * The first iteration starts from the pre-refinement maps: est_left built from the WTA's
+ * d_ref / d_tar by the rule of step 4 (asw_consistency_native with NULL confidences), the
+ * right estimate the WTA's d_tar, the confidences as asw_consistency left them.
+ *
+ * asw_refine_native_params_check: ASW_E_INVALID for a bad rp, ndisp > 65535 or a shard p
+ * (d_begin > 0 or d_end < ndisp); ASW_E_UNSUPPORTED for alpha != 0.085.  asw_ref_h accepts
+ * every (p, rp) this check or asw_refine_params_check accepts. */
+int asw_refine_native_params_check(const asw_params *p, const asw_refine_params *rp);
+/* asw_refine_lut's table (it depends on rp alone) under the native check */
+int asw_refine_native_lut(const asw_params *p, const asw_refine_params *rp, float *lut, void *stream);
+/* est: int32 [H][W] disparity indices; out: [2][H][W] f32 (num/den, den) */
+int asw_ref_v_native(const asw_params *p, const asw_refine_params *rp, const uint8_t *img_rgba, const int32_t *est,
+                     const float *conf, const float *lut, float *out, void *stream);
+/* step 4.  conf_ref / conf_tar (zeroed in place), est_left and post16 may each be NULL;
+ * est_left must not alias d_ref or d_tar.  Reads width, height, ndisp (<= 65535) of p. */
+int asw_consistency_native(const asw_params *p, const int32_t *d_ref, const int32_t *d_tar, float *conf_ref,
+                           float *conf_tar, int32_t *est_left, uint16_t *post16, void *stream);
+/* 3x3 median, clamped borders, of an int32 index map; out: uint16 [H][W].  in != out. */
+int asw_median3_u16(const asw_params *p, const int32_t *in, uint16_t *out, void *stream);
+/* The whole loop on device buffers.  In: the final aggregated volume `cost`; est_left, the
+ * target map d_tar and both confidences as described above, all four updated in place
+ * (d_tar ends as the last asw_wta_ref's target map).  Out (any may be NULL): post16
+ * (written when iters > 0), final16, d_ref of the last asw_wta_ref (iters > 0).
+ * workspace: asw_refine_native_workspace_bytes() of device memory. */
+size_t asw_refine_native_workspace_bytes(const asw_params *p, const asw_refine_params *rp);
+int asw_refine_native(const asw_params *p, const asw_refine_params *rp, const uint8_t *left_rgba,
+                      const uint8_t *right_rgba, const float *cost, int32_t *est_left, int32_t *d_tar, float *conf_ref,
+                      float *conf_tar, void *workspace, uint16_t *post16, uint16_t *final16, int32_t *d_ref,
+                      void *stream);
 
 /* ---- Cross-based matcher with orthogonal integral images: the reference's first method
  * (main.cpp:243-411; K/median.cl, cross.cl, aggregation.cl, integral_h.cl, oii_hcross.cl,
@@ -510,6 +560,27 @@ int asw_match_batch(asw_ctx *ctx, const uint8_t *left_rgba, const uint8_t *right
  * disp_rgba, lr_rgba, lr_red_rgba, disp16, lr16) stays the pre-refinement result
  * (they are copied out before the loop updates its buffers in place). */
 int asw_set_refine(asw_ctx *ctx, const asw_refine_params *rp);
+/* The native refinement loop (asw_refine_native) inside asw_match, for the contexts the
+ * 8-bit loop is not built for (ndisp > 256, ASW_LR_NATIVE) and any other: caller-owned host
+ * arrays, any may be NULL.  asw_set_refine_native checks rp (asw_refine_native_params_check),
+ * copies both structs and allocates the loop's device buffers once; every later asw_match
+ * runs the loop after the pre-refinement outputs have left and fills the registered arrays
+ * (asw_match_batch: pair b at offset b*H*W of each).  rp = NULL or iters = 0: off (the
+ * default; a frame then launches and allocates nothing new); o = NULL with the loop on:
+ * ASW_E_INVALID.  Needs lr_check; ASW_E_INVALID while asw_set_refine is on (and
+ * asw_set_refine returns ASW_E_INVALID while this loop is on): one loop per context.  Its
+ * time is asw_timings.refine.  With asw_set_graph on the loop is captured and replayed like
+ * the 8-bit one.  Multi-shard contexts run the volume scan through the asw_wta_ref_local
+ * protocol and the per-pixel stages on the first shard, bit-identical to one GPU (with
+ * asw_create_rank every rank must switch the loop alike: the all-reduces are collective).
+ * Every other output stays the pre-refinement result. */
+typedef struct asw_refine_native_outputs {
+    uint16_t *final16;      /* [H][W] 3x3 median of the last est_left (asw_disparity16.png)          */
+    uint16_t *post16;       /* [H][W] d_ref of the last iteration where consistent, else
+                               ASW_DISP16_INVALID (asw_consistency_post16.png)                      */
+    int32_t *d_ref, *d_tar; /* [H][W] the last asw_wta_ref's maps                                   */
+} asw_refine_native_outputs;
+int asw_set_refine_native(asw_ctx *ctx, const asw_refine_params *rp, const asw_refine_native_outputs *o);
 /* on != 0: from the next asw_match on, the frame's device work (raw cost to the
  * consistency images, and the refinement loop) is captured once into HIP graphs
  * (hipStreamBeginCapture) and replayed: one launch per graph instead of ~25 (+37 for

@@ -103,6 +103,13 @@ class AswSubpixelOutputs(ctypes.Structure):
     _fields_ = [("disp", ctypes.c_void_p), ("disp_lr", ctypes.c_void_p), ("disp_filled", ctypes.c_void_p)]
 
 
+class AswRefineNativeOutputs(ctypes.Structure):
+    """Mirror of ``asw_refine_native_outputs`` (include/asw.h): host uint16 / int32 [H][W] arrays."""
+
+    _fields_ = [("final16", ctypes.c_void_p), ("post16", ctypes.c_void_p), ("d_ref", ctypes.c_void_p),
+                ("d_tar", ctypes.c_void_p)]
+
+
 class AswRefineParams(ctypes.Structure):
     """Mirror of ``asw_refine_params`` (include/asw.h)."""
 
@@ -210,6 +217,14 @@ SIGNATURES = {
     "asw_refine_workspace_bytes": (ctypes.c_size_t, [PP, RP]),
     "asw_refine": (I, [PP, RP, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "asw_set_refine": (I, [P, RP]),
+    "asw_refine_native_params_check": (I, [PP, RP]),
+    "asw_refine_native_lut": (I, [PP, RP, P, P]),
+    "asw_ref_v_native": (I, [PP, RP, P, P, P, P, P, P]),
+    "asw_consistency_native": (I, [PP, P, P, P, P, P, P, P]),
+    "asw_median3_u16": (I, [PP, P, P, P]),
+    "asw_refine_native_workspace_bytes": (ctypes.c_size_t, [PP, RP]),
+    "asw_refine_native": (I, [PP, RP, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "asw_set_refine_native": (I, [P, RP, P]),
     "asw_set_graph": (I, [P, I]),
     "asw_subpixel": (I, [PP, P, P, P, P]),
     "asw_subpixel_local": (I, [PP, P, P, P, P]),
@@ -323,6 +338,18 @@ def default_refine_params(**kw) -> AswRefineParams:
             raise TypeError(f"unknown asw_refine_params field {k!r}")
         setattr(rp, k, v)
     return rp
+
+
+def refine_is_native(p: AswParams, rp: AswRefineParams) -> bool:
+    """True when (p, rp) needs the native refinement loop (asw_refine_native: indices and
+    uint16 maps) because the 8-bit loop is not built for it (ndisp > 256, ASW_LR_NATIVE).
+    Raises for a pair neither loop accepts."""
+    L = _load()
+    st = L.asw_refine_params_check(ctypes.byref(p), ctypes.byref(rp))
+    if st == ASW_OK:
+        return False
+    check(L.asw_refine_native_params_check(ctypes.byref(p), ctypes.byref(rp)), "asw_refine_native_params_check")
+    return True
 
 
 def default_cross_params(**kw) -> AswCrossParams:

@@ -73,6 +73,14 @@ struct asw_ctx {
     bool refine = false;
     void *rws = nullptr;
     uint8_t *est = nullptr, *post_red = nullptr, *final_rgba = nullptr;  // RGBA8
+    // native refinement loop (asw_set_refine_native): parameters, the registered host arrays,
+    // workspace, the int32 estimate / target / reference maps the loop updates and its uint16 outputs
+    asw_refine_params nrp{};
+    asw_refine_native_outputs nro{};
+    bool nrefine = false;
+    void *nrws = nullptr;
+    int32_t *n_est = nullptr, *n_dt = nullptr, *n_dr = nullptr;
+    uint16_t *n_post16 = nullptr, *n_final16 = nullptr;
     std::vector<hipEvent_t> ev;  // timing events on shard 0's stream
     // asw_set_graph: the frame's device work captured once into HIP graphs, replayed
     bool graph = false;
@@ -324,6 +332,7 @@ int destroy_ctx(asw_ctx *c) {
     (void)hipSetDevice(c->sh[0].device);
     void *bufs[] = {c->red_tmp, c->d_ref, c->d_tar, c->conf_ref, c->conf_tar, c->code_ref, c->code_tar, c->lr,
                     c->lr_red, c->disp, c->disp16, c->lr16, c->rws, c->est, c->post_red, c->final_rgba,
+                    c->nrws, c->n_est, c->n_dt, c->n_dr, c->n_post16, c->n_final16,
                     c->sp_disp, c->sp_lr, c->sp_fill, c->cr_med_l, c->cr_med_r, c->cr_init, c->cr_final,
                     c->cr_arms_l, c->cr_arms_r, c->cr_d0, c->cr_code0, c->cr_code1};
     for (void *b : bufs)
@@ -526,6 +535,51 @@ int sharded_wta(asw_ctx *c) {
                             c->conf_tar, c->code_ref, c->code_tar, s0.stream);
 }
 
+// asw_WTA_REF of a d-sharded frame from the two views' H estimates hl / hr (on shard 0):
+// the scan runs on every shard and is exchanged like the WTA: MIN all-reduces of the left
+// key, the target key and the target second minimum (asw_wta_ref_local protocol).  Maps on
+// shard 0; kl / kt (the 8-bit codes) may be NULL.
+int sharded_wta_ref(asw_ctx *c, const float *hl, const float *hr, int32_t *dr, int32_t *dt, uint8_t *kl,
+                    uint8_t *kt) {
+    const size_t S = frame_pixels(&c->p);
+    Shard &s0 = c->sh[0];
+    hipStream_t st = s0.stream;
+    for (int i = 1; i < c->n; ++i) {  // the estimates to the other shards' devices
+        Shard &s = c->sh[i];
+        HIPCHK(hipMemcpyPeerAsync(s.ref_l, s.device, hl, s0.device, 2 * S * 4, st));
+        HIPCHK(hipMemcpyPeerAsync(s.ref_r, s.device, hr, s0.device, 2 * S * 4, st));
+    }
+    if (c->n > 1) {
+        HIPCHK(hipEventRecord(c->red_done, st));
+        for (int i = 1; i < c->n; ++i) {
+            HIPCHK(hipSetDevice(c->sh[i].device));
+            HIPCHK(hipStreamWaitEvent(c->sh[i].stream, c->red_done, 0));
+        }
+    }
+    for (int i = 0; i < c->n; ++i) {
+        Shard &s = c->sh[i];
+        HIPCHK(hipSetDevice(s.device));
+        ASWCHK(asw_wta_ref_local(&s.p, s.c0, i ? s.ref_l : hl, s.key, s.m1, s.m2, s.stream));
+        HIPCHK(hipMemcpyAsync(s.key_g, s.key, S * 8, hipMemcpyDeviceToDevice, s.stream));
+    }
+    ASWCHK(allreduce_min<int64_t>(c, b_key_g, ncclInt64));
+    for (int i = 0; i < c->n; ++i) {
+        Shard &s = c->sh[i];
+        HIPCHK(hipSetDevice(s.device));
+        ASWCHK(asw_wta_ref_target_local(&s.p, s.c0, i ? s.ref_r : hr, s.key_g, s.tkey, s.t1, s.t2, s.stream));
+        HIPCHK(hipMemcpyAsync(s.tkey_g, s.tkey, S * 8, hipMemcpyDeviceToDevice, s.stream));
+    }
+    ASWCHK(allreduce_min<int64_t>(c, b_tkey_g, ncclInt64));
+    for (int i = 0; i < c->n; ++i) {
+        Shard &s = c->sh[i];
+        HIPCHK(hipSetDevice(s.device));
+        ASWCHK(asw_wta_second(&s.p, s.tkey_g, s.tkey, s.t1, s.t2, s.t2_g, s.stream));
+    }
+    ASWCHK(allreduce_min<float>(c, b_t2_g, ncclFloat32));
+    HIPCHK(hipSetDevice(s0.device));
+    return asw_wta_ref_finalize(&s0.p, s0.key_g, s0.tkey_g, s0.t2_g, dr, dt, c->conf_ref, kl, kt, st);
+}
+
 // The refinement loop (main.cpp:540-617) + median on a d-sharded frame.  The
 // per-pixel stages (asw_ref_v / asw_ref_h, consistency, median) run on shard 0 (in
 // one process per GPU: on every rank, identically); the volume scan (asw_WTA_REF)
@@ -551,40 +605,7 @@ int refine_sharded(asw_ctx *c) {
         ASWCHK(asw_ref_v(p, rp, s0.right, c->code_tar, 1, c->conf_tar, lut, vr, st));
         ASWCHK(asw_ref_h(p, rp, s0.left, c->conf_ref, vl, lut, hl, st));
         ASWCHK(asw_ref_h(p, rp, s0.right, c->conf_tar, vr, lut, hr, st));
-        for (int i = 1; i < c->n; ++i) {  // the estimates to the other shards' devices
-            Shard &s = c->sh[i];
-            HIPCHK(hipMemcpyPeerAsync(s.ref_l, s.device, hl, s0.device, 2 * S * 4, st));
-            HIPCHK(hipMemcpyPeerAsync(s.ref_r, s.device, hr, s0.device, 2 * S * 4, st));
-        }
-        if (c->n > 1) {
-            HIPCHK(hipEventRecord(c->red_done, st));
-            for (int i = 1; i < c->n; ++i) {
-                HIPCHK(hipSetDevice(c->sh[i].device));
-                HIPCHK(hipStreamWaitEvent(c->sh[i].stream, c->red_done, 0));
-            }
-        }
-        for (int i = 0; i < c->n; ++i) {
-            Shard &s = c->sh[i];
-            HIPCHK(hipSetDevice(s.device));
-            ASWCHK(asw_wta_ref_local(&s.p, s.c0, i ? s.ref_l : hl, s.key, s.m1, s.m2, s.stream));
-            HIPCHK(hipMemcpyAsync(s.key_g, s.key, S * 8, hipMemcpyDeviceToDevice, s.stream));
-        }
-        ASWCHK(allreduce_min<int64_t>(c, b_key_g, ncclInt64));
-        for (int i = 0; i < c->n; ++i) {
-            Shard &s = c->sh[i];
-            HIPCHK(hipSetDevice(s.device));
-            ASWCHK(asw_wta_ref_target_local(&s.p, s.c0, i ? s.ref_r : hr, s.key_g, s.tkey, s.t1, s.t2, s.stream));
-            HIPCHK(hipMemcpyAsync(s.tkey_g, s.tkey, S * 8, hipMemcpyDeviceToDevice, s.stream));
-        }
-        ASWCHK(allreduce_min<int64_t>(c, b_tkey_g, ncclInt64));
-        for (int i = 0; i < c->n; ++i) {
-            Shard &s = c->sh[i];
-            HIPCHK(hipSetDevice(s.device));
-            ASWCHK(asw_wta_second(&s.p, s.tkey_g, s.tkey, s.t1, s.t2, s.t2_g, s.stream));
-        }
-        ASWCHK(allreduce_min<float>(c, b_t2_g, ncclFloat32));
-        HIPCHK(hipSetDevice(s0.device));
-        ASWCHK(asw_wta_ref_finalize(&s0.p, s0.key_g, s0.tkey_g, s0.t2_g, dr, dt, c->conf_ref, kl, c->code_tar, st));
+        ASWCHK(sharded_wta_ref(c, hl, hr, dr, dt, kl, c->code_tar));
         ASWCHK(asw_consistency(p, dr, dt, kl, c->code_tar, c->conf_ref, c->conf_tar, c->est, c->post_red, st));
     }
     HIPCHK(hipSetDevice(s0.device));
@@ -621,6 +642,39 @@ int refine_work(asw_ctx *c) {
         return asw_refine(&s0.p, &c->rp, s0.left, s0.right, s0.c0, c->est, c->code_tar, c->conf_ref, c->conf_tar,
                           c->rws, c->post_red, c->final_rgba, nullptr, nullptr, st);
     return refine_sharded(c);
+}
+
+// The native refinement loop (asw_set_refine_native; include/asw.h §native refinement) of a
+// frame: est_left from the WTA's maps by the native rule (the confidences stay as
+// asw_consistency left them), the right estimate a copy of d_tar; then asw_refine_native on
+// a one-shard frame, and on a d-sharded one its stages on shard 0 around sharded_wta_ref.
+int refine_native_work(asw_ctx *c) {
+    const asw_params *p = &c->p;
+    const asw_refine_params *rp = &c->nrp;
+    const size_t S = frame_pixels(p);
+    Shard &s0 = c->sh[0];
+    hipStream_t st = s0.stream;
+    HIPCHK(hipMemcpyAsync(c->n_dt, c->d_tar, S * 4, hipMemcpyDeviceToDevice, st));
+    ASWCHK(asw_consistency_native(p, c->d_ref, c->d_tar, nullptr, nullptr, c->n_est, nullptr, st));
+    if (c->comm == COMM_NONE)
+        return asw_refine_native(&s0.p, rp, s0.left, s0.right, s0.c0, c->n_est, c->n_dt, c->conf_ref, c->conf_tar,
+                                 c->nrws, c->n_post16, c->n_final16, c->n_dr, st);
+    char *ws = static_cast<char *>(c->nrws);
+    float *lut = reinterpret_cast<float *>(ws);
+    ws += (asw_refine_lut_bytes(rp) + 255) / 256 * 256;
+    float *vl = reinterpret_cast<float *>(ws), *vr = vl + 2 * S, *hl = vr + 2 * S, *hr = hl + 2 * S;
+    ASWCHK(asw_refine_native_lut(p, rp, lut, st));
+    for (int it = 0; it < rp->iters; ++it) {
+        HIPCHK(hipSetDevice(s0.device));
+        ASWCHK(asw_ref_v_native(p, rp, s0.left, c->n_est, c->conf_ref, lut, vl, st));
+        ASWCHK(asw_ref_v_native(p, rp, s0.right, c->n_dt, c->conf_tar, lut, vr, st));
+        ASWCHK(asw_ref_h(p, rp, s0.left, c->conf_ref, vl, lut, hl, st));
+        ASWCHK(asw_ref_h(p, rp, s0.right, c->conf_tar, vr, lut, hr, st));
+        ASWCHK(sharded_wta_ref(c, hl, hr, c->n_dr, c->n_dt, nullptr, nullptr));
+        ASWCHK(asw_consistency_native(p, c->n_dr, c->n_dt, c->conf_ref, c->conf_tar, c->n_est, c->n_post16, st));
+    }
+    HIPCHK(hipSetDevice(s0.device));
+    return asw_median3_u16(p, c->n_est, c->n_final16, st);
 }
 
 // The sub-pixel maps (asw_set_subpixel) from the frame's WTA results, on shard 0's
@@ -832,12 +886,24 @@ int match_one(asw_ctx *c, const uint8_t *left_rgba, const uint8_t *right_rgba, a
         }
     }
     HIPCHK(hipEventRecord(ev[e_pre], st));
+    const bool nrefine = c->nrefine && p->lr_check;  // the native loop: never on together with the 8-bit one
     const bool refine = c->refine && p->lr_check;
     if (refine) {  // main.cpp:540-617 on a copy of consistency_error
         if (graphed) ASWCHK(graph_run(st, &c->g_ref, &c->gx_ref, [&] { return refine_work(c); }));
         else ASWCHK(refine_work(c));
+    } else if (nrefine) {
+        if (graphed) ASWCHK(graph_run(st, &c->g_ref, &c->gx_ref, [&] { return refine_native_work(c); }));
+        else ASWCHK(refine_native_work(c));
     }
     HIPCHK(hipEventRecord(ev[e_ref], st));
+    if (nrefine) {
+        const asw_refine_native_outputs &no = c->nro;
+        const size_t off = pair * S;
+        if (no.final16) HIPCHK(hipMemcpyAsync(no.final16 + off, c->n_final16, S * 2, hipMemcpyDeviceToHost, st));
+        if (no.post16) HIPCHK(hipMemcpyAsync(no.post16 + off, c->n_post16, S * 2, hipMemcpyDeviceToHost, st));
+        if (no.d_ref) HIPCHK(hipMemcpyAsync(no.d_ref + off, c->n_dr, S * 4, hipMemcpyDeviceToHost, st));
+        if (no.d_tar) HIPCHK(hipMemcpyAsync(no.d_tar + off, c->n_dt, S * 4, hipMemcpyDeviceToHost, st));
+    }
     if (o && refine) {
         if (o->final_rgba) HIPCHK(hipMemcpyAsync(o->final_rgba, c->final_rgba, S * 4, hipMemcpyDeviceToHost, st));
         if (o->post_red_rgba && c->rp.iters > 0)
@@ -854,7 +920,7 @@ int match_one(asw_ctx *c, const uint8_t *left_rgba, const uint8_t *right_rgba, a
         std::memset(t, 0, sizeof(*t));
         t->h2d = ms_between(ev[0], ev[1]);
         t->total = ms_between(ev[1], ev[e_cons]);
-        t->refine = refine ? ms_between(ev[e_pre], ev[e_ref]) : 0.0;
+        t->refine = refine || nrefine ? ms_between(ev[e_pre], ev[e_ref]) : 0.0;
         t->d2h = ms_between(ev[e_cons], ev[e_pre]) + ms_between(ev[e_ref], ev[e_d2h]);
     } else if (t) {
         std::memset(t, 0, sizeof(*t));
@@ -874,7 +940,7 @@ int match_one(asw_ctx *c, const uint8_t *left_rgba, const uint8_t *right_rgba, a
         t->wta = sharded ? t->exchange : ms_between(ev[e_x], ev[e_wta]);
         t->consistency = ms_between(ev[e_wta], ev[c->sub_on ? e_sub : e_cons]);  // the sub-pixel maps: in no column
         t->total = ms_between(ev[1], ev[e_cons]);
-        t->refine = refine ? ms_between(ev[e_pre], ev[e_ref]) : 0.0;
+        t->refine = refine || nrefine ? ms_between(ev[e_pre], ev[e_ref]) : 0.0;
         t->d2h = ms_between(ev[e_cons], ev[e_pre]) + ms_between(ev[e_ref], ev[e_d2h]);
     }
     return ASW_OK;
@@ -940,6 +1006,61 @@ int asw_device_name(int hip_device, char *buf, int len) {
     return ASW_OK;
 }
 
+// sharded refinement (either loop): the estimates of both views on every shard but the first,
+// and the event that orders their copies; leaves shard 0's device current
+static int alloc_sharded_refine(asw_ctx *c) {
+    const size_t S = frame_pixels(&c->p);
+    for (int i = 1; i < c->n; ++i) {
+        Shard &s = c->sh[i];
+        HIPCHK(hipSetDevice(s.device));
+        if (!s.ref_l) ASWCHK(dev_alloc(&s.ref_l, 2 * S * 4));
+        if (!s.ref_r) ASWCHK(dev_alloc(&s.ref_r, 2 * S * 4));
+    }
+    HIPCHK(hipSetDevice(c->sh[0].device));
+    if (c->n > 1 && !c->red_done) HIPCHK(hipEventCreateWithFlags(&c->red_done, hipEventDisableTiming));
+    return ASW_OK;
+}
+
+static void drop_refine_graph(asw_ctx *c) {
+    if (!c->gx_ref) return;
+    (void)hipGraphExecDestroy(c->gx_ref);
+    (void)hipGraphDestroy(c->g_ref);
+    c->gx_ref = nullptr;
+    c->g_ref = nullptr;
+}
+
+int asw_set_refine_native(asw_ctx *c, const asw_refine_params *rp, const asw_refine_native_outputs *o) {
+    if (!c) return ASW_E_INVALID;
+    if (!rp || rp->iters <= 0) {
+        if (c->nrefine) drop_refine_graph(c);
+        c->nrefine = false;
+        c->nro = asw_refine_native_outputs{};
+        return ASW_OK;
+    }
+    if (!o) return ASW_E_INVALID;
+    ASWCHK(asw_refine_native_params_check(&c->p, rp));
+    if (!c->p.lr_check) return ASW_E_INVALID;  // the loop starts from the LR-checked confidences
+    if (c->refine) return ASW_E_INVALID;       // one loop per context (asw_set_refine)
+    const size_t S = frame_pixels(&c->p);
+    ASWCHK(alloc_sharded_refine(c));
+    const bool same = c->nrefine && std::memcmp(&c->nrp, rp, sizeof *rp) == 0;
+    if (!same) {  // a captured loop used the previous workspace / parameters
+        drop_refine_graph(c);
+        if (c->nrws) (void)hipFree(c->nrws);
+        c->nrws = nullptr;
+        ASWCHK(dev_alloc(&c->nrws, asw_refine_native_workspace_bytes(&c->p, rp)));
+    }
+    if (!c->n_est) ASWCHK(dev_alloc(&c->n_est, S * 4));
+    if (!c->n_dt) ASWCHK(dev_alloc(&c->n_dt, S * 4));
+    if (!c->n_dr) ASWCHK(dev_alloc(&c->n_dr, S * 4));
+    if (!c->n_post16) ASWCHK(dev_alloc(&c->n_post16, S * 2));
+    if (!c->n_final16) ASWCHK(dev_alloc(&c->n_final16, S * 2));
+    c->nrp = *rp;
+    c->nro = *o;
+    c->nrefine = true;
+    return ASW_OK;
+}
+
 int asw_set_refine(asw_ctx *c, const asw_refine_params *rp) {
     if (!c) return ASW_E_INVALID;
     if (!rp || rp->iters <= 0) {
@@ -949,18 +1070,9 @@ int asw_set_refine(asw_ctx *c, const asw_refine_params *rp) {
     const int s = asw_refine_params_check(&c->p, rp);
     if (s != ASW_OK) return s;
     if (!c->p.lr_check) return ASW_E_INVALID;  // the loop starts from the consistency image
+    if (c->nrefine) return ASW_E_INVALID;      // one loop per context (asw_set_refine_native)
     const size_t S = frame_pixels(&c->p);
-    for (int i = 1; i < c->n; ++i) {  // sharded refinement: the estimates of both views on every shard
-        Shard &s = c->sh[i];
-        HIPCHK(hipSetDevice(s.device));
-        if (!s.ref_l) ASWCHK(dev_alloc(&s.ref_l, 2 * S * 4));
-        if (!s.ref_r) ASWCHK(dev_alloc(&s.ref_r, 2 * S * 4));
-    }
-    if (c->n > 1 && !c->red_done) {
-        HIPCHK(hipSetDevice(c->sh[0].device));
-        HIPCHK(hipEventCreateWithFlags(&c->red_done, hipEventDisableTiming));
-    }
-    HIPCHK(hipSetDevice(c->sh[0].device));
+    ASWCHK(alloc_sharded_refine(c));
     const size_t ws = asw_refine_workspace_bytes(&c->p, rp);
     if (c->rws) (void)hipFree(c->rws);
     c->rws = nullptr;

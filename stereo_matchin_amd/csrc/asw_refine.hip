@@ -538,8 +538,10 @@ int asw_ref_v(const asw_params *p, const asw_refine_params *rp, const uint8_t *i
 
 int asw_ref_h(const asw_params *p, const asw_refine_params *rp, const uint8_t *img_rgba, const float *conf,
               const float *in, const float *lut, float *out, void *stream) {
+    // the kernel reads no disparity: what either loop's check accepts (the 8-bit one's
+    // status where both refuse)
     const int s = asw_refine_params_check(p, rp);
-    if (s != ASW_OK) return s;
+    if (s != ASW_OK && asw_refine_native_params_check(p, rp) != ASW_OK) return s;
     if (!img_rgba || !conf || !in || !lut || !out || in == out) return ASW_E_INVALID;
     const dim3 grid((unsigned)((p->width + 255) / 256), (unsigned)p->height);
     hipLaunchKernelGGL(k_ref_h, grid, dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uchar4 *>(img_rgba),

@@ -15,7 +15,10 @@
 //     image before refinement), asw_wta_disparity.png (its `asw_left_wta` image)
 //     and, with the k = 6 refinement iterations of main.cpp:540-617 (--refine K,
 //     0 = off), asw_disparity.png (refined + 3x3 median, main.cpp:619-623) and
-//     asw_consistency_post-reff.png (main.cpp:629-631);
+//     asw_consistency_post-reff.png (main.cpp:629-631); where the 8-bit loop is not built
+//     (D > 256 or --native-lr) the native loop on disparity indices runs instead
+//     (asw_set_refine_native) and writes 16-bit images: asw_disparity16.png (refined + 3x3
+//     median) and asw_consistency_post16.png (65535 = inconsistent);
 //   * errors are printed and the driver continues with the next pair, like ErCheck
 //     (main.cpp:27-30);
 //   * beyond the reference: --devices I,J,... splits the disparity range of every
@@ -75,6 +78,9 @@ void usage() {
                  "                  [--refine K] [--device I | --devices I,J,...] [--png16] [--tsv FILE]\n"
                  "                  [--subpixel] [--cross [--cross-arm N] [--cross-tau N]]\n"
                  "                  [--census [--census-win WxH] [--census-weights A,C]]\n"
+                 "  --refine K  refinement iterations + 3x3 median (default 6, 0 = off): asw_disparity.png and\n"
+                 "              asw_consistency_post-reff.png; with --ndisp > 256 or --native-lr the loop runs on disparity\n"
+                 "              indices and writes asw_disparity16.png and asw_consistency_post16.png (65535 = inconsistent)\n"
                  "  --census    the census / AD-census cost A * min(AD, tau) + C * hamming in place of the AD raw cost\n"
                  "              (robust to a gain / offset between the views); window W, H in 3, 5, 7, 9 but 9x9\n"
                  "              (default 9x7), weights A 0..64, C 1..1024 (default 1,8; A = 0: census only)\n"
@@ -241,11 +247,13 @@ int main(int argc, char **argv) {
             continue;
         }
         // the loop runs on d-sharded contexts too (asw_set_refine: its asw_WTA_REF scan is
-        // exchanged like the WTA); it feeds back 8-bit codes, so D > 256 has none
-        const bool refine = o.refine > 0 && p.lr_check && !wide;
-        if (o.refine > 0 && !refine)
-            std::fprintf(stderr, "%s: refinement skipped (%s)\n", folder.c_str(),
-                         !p.lr_check ? "it needs the LR check" : "D > 256: the loop re-reads 8-bit codes");
+        // exchanged like the WTA); it feeds back 8-bit codes, so D > 256 and the native LR
+        // rule take the native loop on indices (asw_set_refine_native, 16-bit images)
+        const bool native = p.lr_mode == ASW_LR_NATIVE;
+        const bool refine = o.refine > 0 && p.lr_check && !native;
+        const bool nrefine = o.refine > 0 && p.lr_check && native;
+        if (o.refine > 0 && !p.lr_check)
+            std::fprintf(stderr, "%s: refinement skipped (it needs the LR check)\n", folder.c_str());
         if (refine) {
             asw_refine_params rp;
             asw_refine_params_default(&rp);
@@ -253,6 +261,24 @@ int main(int argc, char **argv) {
             st = asw_set_refine(ctx, &rp);
             if (st != ASW_OK) {
                 std::fprintf(stderr, "%s: asw_set_refine: %s\n", folder.c_str(), asw_strerror(st));
+                ++failures;
+                asw_destroy(ctx);
+                continue;
+            }
+        }
+        const size_t S = (size_t)p.width * p.height;
+        std::vector<uint16_t> fin16(nrefine ? S : 0), post16(nrefine ? S : 0);
+        if (nrefine) {  // registered once, filled by every asw_match
+            asw_refine_params rp;
+            asw_refine_params_default(&rp);
+            rp.iters = o.refine;
+            asw_refine_native_outputs no;
+            std::memset(&no, 0, sizeof no);
+            no.final16 = fin16.data();
+            no.post16 = post16.data();
+            st = asw_set_refine_native(ctx, &rp, &no);
+            if (st != ASW_OK) {
+                std::fprintf(stderr, "%s: asw_set_refine_native: %s\n", folder.c_str(), asw_strerror(st));
                 ++failures;
                 asw_destroy(ctx);
                 continue;
@@ -271,7 +297,6 @@ int main(int argc, char **argv) {
                 continue;
             }
         }
-        const size_t S = (size_t)p.width * p.height;
         std::vector<uint8_t> disp(S * 4), lr(S * 4), lr_red(S * 4), fin(S * 4), post(S * 4);
         std::vector<uint16_t> disp16(png16 ? S : 0), lr16(png16 ? S : 0);
         // sub-pixel float maps: registered once, filled by every asw_match
@@ -390,6 +415,15 @@ int main(int argc, char **argv) {
             e = asw_host::png_save16(dir + "/asw_wta_disparity16.png", disp16.data(), L.width, L.height);
             if (e.empty() && p.lr_check)
                 e = asw_host::png_save16(dir + "/asw_consistency16.png", lr16.data(), L.width, L.height);
+            if (!e.empty()) {
+                std::fprintf(stderr, "%s: %s\n", folder.c_str(), e.c_str());
+                ++failures;
+            }
+        }
+        if (nrefine) {
+            e = asw_host::png_save16(dir + "/asw_disparity16.png", fin16.data(), L.width, L.height);
+            if (e.empty())
+                e = asw_host::png_save16(dir + "/asw_consistency_post16.png", post16.data(), L.width, L.height);
             if (!e.empty()) {
                 std::fprintf(stderr, "%s: %s\n", folder.c_str(), e.c_str());
                 ++failures;

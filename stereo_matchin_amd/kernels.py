@@ -630,3 +630,84 @@ def refine(p: AswParams, rp, left, right, cost, est_left_rgba, code_tar, conf_re
                                      _ptr(est_left_rgba), _ptr(code_tar), _ptr(conf_ref), _ptr(conf_tar), _ptr(ws),
                                      _ptr(post), _ptr(final), _ptr(d_ref), _ptr(d_tar), _stream(dev)), "asw_refine")
     return {"post_red_rgba": post, "final_rgba": final, "d_ref": d_ref, "d_tar": d_tar}
+
+
+# ------------------------------------------------------------------ native refinement
+# The loop above on disparity indices (include/asw.h §native refinement): int32 estimate
+# maps in, uint16 maps out, any ndisp <= 65535 and either LR mode.  asw_ref_h and
+# asw_WTA_REF are shared with the 8-bit loop.
+
+def refine_native_lut(p: AswParams, rp, device) -> torch.Tensor:
+    """asw_refine_native_lut: refine_lut's table under the native parameter check."""
+    lut = torch.empty((rp.taps // 2 + 1, 766), dtype=torch.float32, device=device)
+    _lib.check(_lib.lib().asw_refine_native_lut(ctypes.byref(p), ctypes.byref(rp), _ptr(lut), _stream(device)),
+               "asw_refine_native_lut")
+    return lut
+
+
+def asw_ref_v_native(p: AswParams, rp, img: torch.Tensor, est: torch.Tensor, conf: torch.Tensor, lut: torch.Tensor,
+                     out: torch.Tensor | None = None):
+    """asw_ref_v with ``Dv = (float)est[q]``: ``est`` is an int32 [H][W] index map."""
+    H, W = p.height, p.width
+    _expect(img, (H, W, 4), torch.uint8, "img")
+    _expect(est, (H, W), torch.int32, "est")
+    _expect(conf, (H, W), torch.float32, "conf")
+    _expect(lut, (rp.taps // 2 + 1, 766), torch.float32, "lut")
+    if out is None:
+        out = torch.empty((2, H, W), dtype=torch.float32, device=img.device)
+    _expect(out, (2, H, W), torch.float32, "out")
+    _lib.check(_lib.lib().asw_ref_v_native(ctypes.byref(p), ctypes.byref(rp), _ptr(img), _ptr(est), _ptr(conf),
+                                           _ptr(lut), _ptr(out), _stream(img.device)), "asw_ref_v_native")
+    return out
+
+
+def consistency_native(p: AswParams, d_ref: torch.Tensor, d_tar: torch.Tensor, conf_ref: torch.Tensor | None = None,
+                       conf_tar: torch.Tensor | None = None):
+    """asw_consistency_native: ``|d_ref - d_tar| <= 1``.  Zeroes the given confidences in
+    place where it fails; returns ``(est_left int32, post16)`` (post16 as int16 storage of the
+    uint16 map, 0xFFFF = inconsistent)."""
+    H, W = p.height, p.width
+    _expect(d_ref, (H, W), torch.int32, "d_ref")
+    _expect(d_tar, (H, W), torch.int32, "d_tar")
+    for c in (conf_ref, conf_tar):
+        if c is not None:
+            _expect(c, (H, W), torch.float32, "conf")
+    est = torch.empty_like(d_ref)
+    post16 = torch.empty((H, W), dtype=torch.int16, device=d_ref.device)
+    _lib.check(_lib.lib().asw_consistency_native(ctypes.byref(p), _ptr(d_ref), _ptr(d_tar), _ptr(conf_ref),
+                                                 _ptr(conf_tar), _ptr(est), _ptr(post16), _stream(d_ref.device)),
+               "asw_consistency_native")
+    return est, post16
+
+
+def Median16(p: AswParams, est: torch.Tensor) -> torch.Tensor:
+    """asw_median3_u16: 3x3 clamp-to-edge median of an int32 index map, uint16 in int16 storage."""
+    _expect(est, (p.height, p.width), torch.int32, "est")
+    out = torch.empty((p.height, p.width), dtype=torch.int16, device=est.device)
+    _lib.check(_lib.lib().asw_median3_u16(ctypes.byref(p), _ptr(est), _ptr(out), _stream(est.device)),
+               "asw_median3_u16")
+    return out
+
+
+def refine_native(p: AswParams, rp, left, right, cost, est_left, d_tar, conf_ref, conf_tar) -> dict:
+    """The whole native loop (asw_refine_native).  est_left, d_tar (int32), conf_ref and
+    conf_tar are updated in place; returns post16 / final16 (uint16 in int16 storage) and
+    the last asw_WTA_REF maps (``d_tar`` is the updated argument)."""
+    H, W = p.height, p.width
+    dev = cost.device
+    _expect(cost, cost_shape(p), torch.float32, "cost")
+    for m in (est_left, d_tar):
+        _expect(m, (H, W), torch.int32, "index map")
+    for m in (conf_ref, conf_tar):
+        _expect(m, (H, W), torch.float32, "conf")
+    _lib.check(_lib.lib().asw_refine_native_params_check(ctypes.byref(p), ctypes.byref(rp)),
+               "asw_refine_native_params_check")
+    ws = torch.empty(int(_lib.lib().asw_refine_native_workspace_bytes(ctypes.byref(p), ctypes.byref(rp))),
+                     dtype=torch.uint8, device=dev)
+    post = torch.full((H, W), -1, dtype=torch.int16, device=dev)
+    final = torch.empty((H, W), dtype=torch.int16, device=dev)
+    d_ref = torch.empty((H, W), dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().asw_refine_native(ctypes.byref(p), ctypes.byref(rp), _ptr(left), _ptr(right), _ptr(cost),
+                                            _ptr(est_left), _ptr(d_tar), _ptr(conf_ref), _ptr(conf_tar), _ptr(ws),
+                                            _ptr(post), _ptr(final), _ptr(d_ref), _stream(dev)), "asw_refine_native")
+    return {"post16": post, "final16": final, "d_ref": d_ref, "d_tar": d_tar, "est_left": est_left}

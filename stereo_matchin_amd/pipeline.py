@@ -170,10 +170,19 @@ class StereoMatcher:
         """The refinement loop + median (main.cpp:540-623) after ``match`` (needs its LR
         check).  ``res``'s lr image, target codes and confidences are refined in place
         like the reference's buffers; returns post_red_rgba (asw_consistency_post-reff),
-        final_rgba (asw_disparity.png) and the last asw_WTA_REF maps."""
+        final_rgba (asw_disparity.png) and the last asw_WTA_REF maps.
+
+        Where the 8-bit loop is not built (ndisp > 256, ASW_LR_NATIVE) the native loop runs
+        instead (asw_refine_native, on indices): ``res``'s confidences are refined in place,
+        its maps stay; returns final16 / post16 (uint16 maps in int16 storage, 0xFFFF =
+        inconsistent), the last asw_WTA_REF maps d_ref / d_tar and est_left."""
         if res.lr_rgba is None:
             raise ValueError("refinement starts from the consistency image: match() with lr_check")
         rp = _lib.default_refine_params() if rp is None else rp
+        if _lib.refine_is_native(self.p, rp):
+            est_left, _ = K.consistency_native(self.p, res.d_ref, res.d_tar)
+            return K.refine_native(self.p, rp, left, right, res.cost, est_left, res.d_tar.clone(), res.conf_ref,
+                                   res.conf_tar)
         return K.refine(self.p, rp, left, right, res.cost, res.lr_rgba, res.code_tar, res.conf_ref, res.conf_tar)
 
 
@@ -274,8 +283,20 @@ class FrameContext:
             _lib.check(self.L.asw_create_multi(ctypes.byref(self.p), arr, len(devices), ctypes.byref(self.ctx)),
                        "asw_create_multi")
         self.cross = None  # set_cross: (AswCrossParams, want timings)
+        # refine: an AswRefineParams, main.cpp:540-623 inside asw_match; where the 8-bit loop is
+        # not built for the context (ndisp > 256, ASW_LR_NATIVE) the native loop on indices
+        # (asw_set_refine_native), whose maps arrive as final16 / post16 / refine_d_ref / refine_d_tar
+        self.refine_native = None
+        if refine is not None and refine.iters > 0 and _lib.refine_is_native(self.p, refine):
+            self.refine_native = _lib.AswRefineParams(refine.iters, refine.taps, refine.gamma_c, refine.gamma_g,
+                                                      refine.alpha)
+            # validated here with empty outputs; match_batch registers each call's arrays
+            _lib.check(self.L.asw_set_refine_native(self.ctx, ctypes.byref(self.refine_native),
+                                                    ctypes.byref(_lib.AswRefineNativeOutputs())),
+                       "asw_set_refine_native")
+            refine = None
         self.refine = refine is not None
-        if refine is not None:  # an AswRefineParams: main.cpp:540-623 inside asw_match
+        if refine is not None:
             _lib.check(self.L.asw_set_refine(self.ctx, ctypes.byref(refine)), "asw_set_refine")
         if graph:  # asw_set_graph: capture the device work into HIP graphs, replay them
             _lib.check(self.L.asw_set_graph(self.ctx, 1), "asw_set_graph")
@@ -375,15 +396,25 @@ class FrameContext:
         if self.cross is not None and B:
             cr, ctim, co = self._cross_outputs(B)
             _lib.check(self.L.asw_set_cross(self.ctx, ctypes.byref(self.cross[0]), ctypes.byref(co)), "asw_set_cross")
+        nat = {}
+        if self.refine_native is not None and B:
+            nat = {"final16": np.empty((B, H, W), np.uint16), "post16": np.empty((B, H, W), np.uint16),
+                   "refine_d_ref": np.empty((B, H, W), np.int32), "refine_d_tar": np.empty((B, H, W), np.int32)}
+            no = _lib.AswRefineNativeOutputs(*[v.ctypes.data for v in nat.values()])
+            _lib.check(self.L.asw_set_refine_native(self.ctx, ctypes.byref(self.refine_native), ctypes.byref(no)),
+                       "asw_set_refine_native")
         try:
             _lib.check(self.L.asw_match_batch(self.ctx, lefts.ctypes.data, rights.ctypes.data, B, oarr, tarr),
                        "asw_match_batch")
         finally:
             if sub:  # the registered arrays are this call's: off again
                 self.L.asw_set_subpixel(self.ctx, None)
+            if nat:  # this call's arrays leave the context; the loop stays on
+                self.L.asw_set_refine_native(self.ctx, ctypes.byref(self.refine_native),
+                                             ctypes.byref(_lib.AswRefineNativeOutputs()))
             if cr:  # this call's arrays leave the context; the matcher stays on
                 self.L.asw_set_cross(self.ctx, ctypes.byref(self.cross[0]), ctypes.byref(_lib.AswCrossOutputs()))
-        for k, v in {**sub, **cr}.items():
+        for k, v in {**sub, **cr, **nat}.items():
             for b in range(B):
                 outs[b][k] = v[b]
         if ctim is not None:
