@@ -186,7 +186,8 @@ int asw_support_lut(const asw_params *p, float *lut, void *stream);
 
 /* replaces asw_vSupport / asw_hSupport (K/asw_vsupport.cl:3-27, K/asw_hsupport.cl:3-28),
  * launched at main.cpp:469-484 (once per image and direction).  RGB contexts only
- * (ASW_E_INVALID for ASW_COLOR_LAB: use asw_lab + asw_support_lab). */
+ * (ASW_E_INVALID for ASW_COLOR_LAB: use asw_lab + asw_support_lab).  The padding taps
+ * i >= taps of every pixel are written 0 (asw_support_all and asw_support_lab too). */
 int asw_support(const asw_params *p, int dir, const uint8_t *img_rgba, const float *lut, float *w,
                 void *stream);
 
@@ -208,7 +209,11 @@ int asw_support_lab(const asw_params *p, int dir, const float *lab, float *w, vo
 /* replaces asw_vCostAggregation / asw_hCostAggregation (K/asw_vcost_aggregation.cl:11-44,
  * K/asw_hcost_aggregation.cl:12-44), launched at main.cpp:494-509.  One pass over
  * every local plane: cout = sum_i wl_i*wr_i(xr)*cin_i / sum_i wl_i*wr_i(xr).
- * The reference's dead `denom` output is not produced.  cin != cout. */
+ * The reference's dead `denom` output is not produced.  cin != cout.
+ * Padding planes k >= d_end - d_begin of cout are UNSPECIFIED in every pass entry point
+ * (asw_aggregate_pass, _den, _den16, asw_aggregate, asw_aggregate_den): the kernels carry
+ * them along, computed from cin's padding planes (NaN or 0xFFFF there comes out as NaN or
+ * a large value).  No valid plane depends on a padding plane of cin, cout or den. */
 int asw_aggregate_pass(const asw_params *p, int dir, const float *wl, const float *wr, const float *cin,
                        float *cout, void *stream);
 
@@ -217,7 +222,9 @@ int asw_aggregate_pass(const asw_params *p, int dir, const float *wl, const floa
  * (K/asw_vcost_aggregation.cl:38, written to its dead asw_denom buffer); it does
  * not depend on the cost, so ASW_DEN_WRITE stores it during a pass and
  * ASW_DEN_READ reuses it in the later passes of the same direction (same
- * supports).  Results are bit-identical in every mode. */
+ * supports).  Results are bit-identical in every mode.  The padding planes of `den` are
+ * UNSPECIFIED: ASW_DEN_WRITE writes them (the sum at the disparities past d_end, which no
+ * valid plane uses) and ASW_DEN_READ reads them into cout's padding planes only. */
 #define ASW_DEN_NONE 0  /* compute den, do not touch `den` (may be NULL) */
 #define ASW_DEN_WRITE 1 /* compute den and store it to `den`            */
 #define ASW_DEN_READ 2  /* take den from `den` (written by a DEN_WRITE pass of this direction) */

@@ -13,8 +13,10 @@ import pytest
 import census_ref as CR
 import subpixel_ref as SR
 from conftest import ROOT, plane_major
+from guarded import guarded_kernels  # noqa: F401  (a fixture, used by name)
 
-pytestmark = pytest.mark.gpu
+# every output the wrappers allocate is guarded and poisoned (tests/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_kernels")]
 
 F = np.float32
 PKG = os.path.join(ROOT, "stereo_matchin_amd")

@@ -13,8 +13,10 @@ import pytest
 
 import cross_ref as CR
 from conftest import GOLDEN, ROOT, SCENES, load_scene
+from guarded import guarded_kernels  # noqa: F401  (a fixture, used by name)
 
-pytestmark = pytest.mark.gpu
+# every output the wrappers allocate is guarded and poisoned (tests/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_kernels")]
 
 MAX_MISMATCH_FRAC = 0.0025  # tests/test_cross.py: the ASW oracle's bound against the device images
 ART_ROWS = 341              # art is pinned on rows [0, 341)

@@ -12,8 +12,10 @@ import numpy as np
 import pytest
 
 from conftest import load_scene, pixel_major, plane_major
+from guarded import guarded_kernels  # noqa: F401  (a fixture, used by name)
 
-pytestmark = pytest.mark.gpu
+# every output the wrappers allocate is guarded and poisoned (tests/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_kernels")]
 
 COST_TOL = 1e-4  # north star: "within 1e-4 on the float aggregated cost" (relative to max(1,|b|))
 

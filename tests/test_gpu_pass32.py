@@ -11,8 +11,10 @@ import numpy as np
 import pytest
 
 from conftest import pixel_major, plane_major
+from guarded import guarded_kernels  # noqa: F401  (a fixture, used by name)
 
-pytestmark = pytest.mark.gpu
+# every output the wrappers allocate is guarded and poisoned (tests/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_kernels")]
 
 
 def _t(a, dev):

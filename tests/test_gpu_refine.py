@@ -7,9 +7,11 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, load_scene, pixel_major
+from guarded import guarded_kernels  # noqa: F401  (a fixture, used by name)
 from wta_shard_ref import case_seed, refine_estimates, well_volume
 
-pytestmark = pytest.mark.gpu
+# every output the wrappers allocate is guarded and poisoned (tests/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_kernels")]
 
 
 def _t(a, dev):

@@ -12,8 +12,10 @@ import pytest
 
 import subpixel_ref as SR
 from conftest import ROOT, load_scene
+from guarded import guarded_kernels  # noqa: F401  (a fixture, used by name)
 
-pytestmark = pytest.mark.gpu
+# every output the wrappers allocate is guarded and poisoned (tests/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_kernels")]
 
 F = np.float32
 PKG = os.path.join(ROOT, "stereo_matchin_amd")

@@ -15,9 +15,11 @@ import numpy as np
 import pytest
 
 from conftest import pixel_major
+from guarded import guarded_kernels  # noqa: F401  (a fixture, used by name)
 from wta_shard_ref import CASES, case_id, case_seed, shard_case, well_volume
 
-pytestmark = pytest.mark.gpu
+# every output the wrappers allocate is guarded and poisoned (tests/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_kernels")]
 
 
 def _t(a, dev):

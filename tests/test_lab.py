@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import load_scene
+from guarded import guarded_kernels  # noqa: F401  (a fixture, used by name)
 
 # published CIE L*a*b* (D65, 2 deg) of the sRGB primaries / neutrals
 KNOWN = {
@@ -51,6 +52,7 @@ def test_oracle_support_lab_centre_tap_is_one(oracle):
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("guarded_kernels")
 def test_lab_exhaustive_bit_exact(gpu, oracle):
     """Every one of the 2^24 RGB colours, HIP vs oracle, bit for bit."""
     import torch
@@ -69,6 +71,7 @@ def test_lab_exhaustive_bit_exact(gpu, oracle):
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("guarded_kernels")
 @pytest.mark.parametrize("T", [5, 33, 35])
 def test_support_lab_bit_exact(gpu, oracle, T):
     import torch
@@ -86,6 +89,7 @@ def test_support_lab_bit_exact(gpu, oracle, T):
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("guarded_kernels")
 def test_rgb_support_entry_rejects_lab_context(gpu):
     import torch
     from stereo_matchin_amd import kernels as K, make_params
@@ -97,6 +101,7 @@ def test_rgb_support_entry_rejects_lab_context(gpu):
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("guarded_kernels")
 @pytest.mark.parametrize("scene,D,T,tau", [("tsukuba", 16, 5, 765.0), ("teddy", 64, 35, 60.0)])
 def test_e2e_lab_tad_bit_exact(gpu, oracle, scene, D, T, tau):
     """Full pipeline with the CIELab colour term (and truncated AD) vs the oracle."""
@@ -115,6 +120,7 @@ def test_e2e_lab_tad_bit_exact(gpu, oracle, scene, D, T, tau):
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("guarded_kernels")
 def test_frame_api_lab(gpu, oracle):
     """asw_match of a LAB context (the frame API allocates and converts itself)."""
     import ctypes
