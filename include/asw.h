@@ -75,7 +75,8 @@ typedef struct asw_params {
  * ignores flags. */
 #define ASW_FLAG_COMM_LOCAL 0x20     /* asw_create_multi: the device-local exchange even for distinct ids */
 #define ASW_FLAG_RAW_F32 0x40        /* keep the float raw-cost volume (asw_raw_cost) where the uint16 one
-                                        (asw_raw_cost16 + asw_aggregate_pass_den16) is the default    */
+                                        (asw_raw_cost16 + asw_aggregate_pass_den16) is the default;
+                                        ignored while asw_set_sgm is on (SGM reads the uint16 volume) */
 #define ASW_FLAG_ALL 0x60
 
 void asw_params_default(asw_params *p);
@@ -100,7 +101,9 @@ int asw_last_hip_error(void); /* hipError_t of the last ASW_E_HIP */
  *      asw_census16_supported) and asw_set_census with its own asw_census_params struct; the
  *      native refinement loop (asw_refine_native_*, asw_ref_v_native, asw_consistency_native,
  *      asw_median3_u16, asw_refine_native) and asw_set_refine_native with its own
- *      asw_refine_native_outputs struct. */
+ *      asw_refine_native_outputs struct; the semi-global matching aggregator (asw_sgm_params_default,
+ *      asw_sgm_params_check, asw_sgm_workspace_bytes, asw_sgm_path, asw_sgm) and asw_set_sgm with
+ *      its own asw_sgm_params struct. */
 #define ASW_ABI_VERSION 4
 int asw_abi_version(void);
 
@@ -180,6 +183,42 @@ int asw_census_cost16(const asw_params *p, const asw_census_params *cp, const ui
                       const uint8_t *right_rgba, const uint64_t *cen_left, const uint64_t *cen_right, uint16_t *cost,
                       void *stream);
 int asw_census16_supported(const asw_params *p, const asw_census_params *cp);
+
+/* ---- semi-global matching (Hirschmueller 2008) on the uint16 raw-cost volume (no reference
+ * counterpart: the reference's only aggregator is the iterated ASW pass).  Every operation is
+ * an integer one.  Input: a whole-volume raw cost C, uint16 [H][W][Dp], as
+ * asw_raw_cost16 or asw_census_cost16 writes it; padding planes d >= ndisp never reach a
+ * result.  Path k has the step (dx, dy); the predecessor of p = (x, y) is q = (x-dx, y-dy):
+ *   k  0: (+1, 0)  1: (-1, 0)  2: (0, +1)  3: (0, -1)  4: (+1, +1)  5: (-1, -1)  6: (-1, +1)  7: (+1, -1)
+ *   q outside the image:  L_k(p, d) = C(p, d)
+ *   else, m = min_{j < ndisp} L_k(q, j):
+ *     L_k(p, d) = C(p, d) + min(L_k(q, d), L_k(q, d-1) + P1, L_k(q, d+1) + P1, m + P2) - m
+ *     (the d-1 term absent at d = 0, the d+1 term at d = ndisp-1)
+ * so C <= L_k <= C + P2.  S(p, d) = sum of L_k over k < paths (4: k = 0..3; 8: k = 0..7) is
+ * below 2^24: the output volume, float32 [H][W][Dp], holds (float)S exactly, and every float
+ * add of partial sums is exact, so the order of the paths is free.  The first-argmin WTA and
+ * everything after it read this volume like an aggregated one.
+ * asw_sgm_params_check: ASW_E_INVALID for paths not 4 or 8, penalties outside
+ * 0 <= p1 <= p2 <= 1048576, a p that fails asw_params_check, or a shard p (d_begin > 0 or
+ * d_end < ndisp: m is a minimum over every disparity).  Offsets are 64-bit: no accepted shape
+ * overflows them (a pitch above 65536 planes is ASW_E_UNSUPPORTED at launch).
+ *   asw_sgm_path: path k alone (0 <= k < 8 whatever sp->paths, else ASW_E_INVALID).
+ *     accumulate == 0: sum = (float)L_k on the valid planes, +0 on the padding planes;
+ *     accumulate != 0: sum = sum + (float)L_k on the valid planes, padding planes kept.
+ *   asw_sgm: the whole S of sp->paths, padding planes +0.  workspace: asw_sgm_workspace_bytes
+ *     of device memory (0 today: NULL is accepted then, ASW_E_INVALID otherwise).
+ * cost16 and sum must not alias. */
+typedef struct asw_sgm_params {
+    int paths;   /* 4 or 8; default 8                        */
+    int p1, p2;  /* 0 <= p1 <= p2 <= 1048576; default 16, 128 */
+} asw_sgm_params;
+void asw_sgm_params_default(asw_sgm_params *sp);
+int asw_sgm_params_check(const asw_params *p, const asw_sgm_params *sp);
+size_t asw_sgm_workspace_bytes(const asw_params *p, const asw_sgm_params *sp);
+int asw_sgm_path(const asw_params *p, const asw_sgm_params *sp, int k, const uint16_t *cost16, float *sum,
+                 int accumulate, void *stream);
+int asw_sgm(const asw_params *p, const asw_sgm_params *sp, const uint16_t *cost16, float *sum, void *workspace,
+            void *stream);
 
 /* support-weight table (the exp of K/asw_vsupport.cl:22-25 for every (|delta|, SAD)) */
 int asw_support_lut(const asw_params *p, float *lut, void *stream);
@@ -651,6 +690,25 @@ int asw_set_cross(asw_ctx *ctx, const asw_cross_params *cp, const asw_cross_outp
  * asw_match captures again.  Refinement, the sub-pixel maps, the LR modes and the
  * cross-based stages (which keep their own cost) are untouched. */
 int asw_set_census(asw_ctx *ctx, const asw_census_params *cp);
+/* Semi-global matching (asw_sgm) in place of the supports and the 2r ASW passes of later
+ * asw_match calls (sp = NULL: off, the default; a frame then launches and allocates nothing
+ * new).  asw_set_sgm checks sp against the context (asw_sgm_params_check) and copies it; the
+ * workspace (asw_sgm_workspace_bytes) is allocated once.  A frame then writes the raw cost in
+ * its uint16 form (asw_raw_cost16, or with census on asw_census x 2 and asw_census_cost16)
+ * into one of the context's two cost volumes and asw_sgm's sums into the other; the WTA and
+ * everything after it (LR check, 16-bit and sub-pixel maps, both refinement loops,
+ * asw_outputs.cost) read that volume.  The supports and passes are not launched: taps and
+ * iters are not read (any tap count, iters = 0 included), and ASW_FLAG_RAW_F32 is ignored.
+ * ASW_E_UNSUPPORTED: a context with more than one shard (m is a minimum over every
+ * disparity), and a cost without a uint16 form (asw_raw_cost16's / asw_census_cost16's
+ * ASW_E_UNSUPPORTED: a fractional tad_tau below 765 with an AD term); asw_set_census returns
+ * ASW_E_UNSUPPORTED for such a form while SGM is on.  The context is unchanged after an error.
+ * Timings: the SGM launches are asw_timings.aggregation_total; support, v_pass_mean and
+ * h_pass_mean are 0.  With asw_set_graph on the launches are inside the captured frame:
+ * asw_set_sgm drops a captured frame graph, the next asw_match captures again.  The
+ * refinement penalty 0.085 * den * |val - d| was tuned against ASW-scale costs: the loops
+ * run on the sums unchanged, their quality there is not claimed. */
+int asw_set_sgm(asw_ctx *ctx, const asw_sgm_params *sp);
 
 #ifdef __cplusplus
 }

@@ -134,6 +134,16 @@ class AswCensusParams(ctypes.Structure):
         return AswCensusParams(self.win_w, self.win_h, self.ad_weight, self.census_weight)
 
 
+class AswSgmParams(ctypes.Structure):
+    """Mirror of ``asw_sgm_params`` (include/asw.h): the number of paths (4 or 8) and the
+    penalties ``0 <= p1 <= p2 <= 1048576`` of semi-global matching."""
+
+    _fields_ = [("paths", ctypes.c_int), ("p1", ctypes.c_int), ("p2", ctypes.c_int)]
+
+    def copy(self) -> "AswSgmParams":
+        return AswSgmParams(self.paths, self.p1, self.p2)
+
+
 class AswCrossTimings(ctypes.Structure):
     """Mirror of ``asw_cross_timings``: the reference's columns (main.cpp:394-410), ms."""
 
@@ -169,6 +179,7 @@ PP = ctypes.POINTER(AswParams)
 RP = ctypes.POINTER(AswRefineParams)
 CP = ctypes.POINTER(AswCrossParams)
 NP = ctypes.POINTER(AswCensusParams)
+SP = ctypes.POINTER(AswSgmParams)
 I = ctypes.c_int
 
 # name -> (restype, argtypes).  Every function declared in include/asw.h.
@@ -251,6 +262,12 @@ SIGNATURES = {
     "asw_census_cost16": (I, [PP, NP, P, P, P, P, P, P]),
     "asw_census16_supported": (I, [PP, NP]),
     "asw_set_census": (I, [P, NP]),
+    "asw_sgm_params_default": (None, [SP]),
+    "asw_sgm_params_check": (I, [PP, SP]),
+    "asw_sgm_workspace_bytes": (ctypes.c_size_t, [PP, SP]),
+    "asw_sgm_path": (I, [PP, SP, I, P, P, I, P]),
+    "asw_sgm": (I, [PP, SP, P, P, P, P]),
+    "asw_set_sgm": (I, [P, SP]),
     "asw_tune_set": (I, [I, I]),
     "asw_pass_kernel": (I, [I, I, ctypes.c_char_p, I]),
     "asw_device_name": (I, [I, ctypes.c_char_p, I]),
@@ -380,6 +397,25 @@ def census_params_of(census) -> AswCensusParams | None:
     if census is None or census is False:
         return None
     return default_census_params() if census is True else census.copy()
+
+
+def default_sgm_params(**kw) -> AswSgmParams:
+    """The default semi-global matching parameters (8 paths, P1 16, P2 128), overridable."""
+    sp = AswSgmParams()
+    _load().asw_sgm_params_default(ctypes.byref(sp))
+    for k, v in kw.items():
+        if not hasattr(sp, k):
+            raise TypeError(f"unknown asw_sgm_params field {k!r}")
+        setattr(sp, k, v)
+    return sp
+
+
+def sgm_params_of(sgm) -> AswSgmParams | None:
+    """The ``sgm=`` keyword of the matchers: None / False (off), True (the defaults) or an
+    AswSgmParams."""
+    if sgm is None or sgm is False:
+        return None
+    return default_sgm_params() if sgm is True else sgm.copy()
 
 
 def disp_pitch(p: AswParams) -> int:

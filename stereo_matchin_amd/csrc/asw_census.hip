@@ -225,6 +225,13 @@ int launch_census_cost(bool u16, const asw_params *p, const asw_census_params *c
 }
 
 }  // namespace
+
+int census_cost16_check(const asw_params *p, const asw_census_params *cp) {
+    if (!census16_exact(p, cp)) return ASW_E_UNSUPPORTED;
+    const size_t lds = (size_t)3 * 4 * cc_phase_stride(asw_disp_pitch(p)) * sizeof(unsigned);
+    return lds > 64 * 1024 ? ASW_E_UNSUPPORTED : ASW_OK;
+}
+
 }  // namespace asw
 
 using namespace asw;
@@ -296,7 +303,7 @@ int asw_census_cost(const asw_params *p, const asw_census_params *cp, const uint
 int asw_census16_supported(const asw_params *p, const asw_census_params *cp) {
     if (asw_census_params_check(p, cp) != ASW_OK) return 0;
     // exact, and read by a ring-kernel first V pass (asw_aggregate_pass_den16)
-    return census16_exact(p, cp) && p->iters >= 1 && ring_taps(p->taps) ? 1 : 0;
+    return census_cost16_check(p, cp) == ASW_OK && p->iters >= 1 && ring_taps(p->taps) ? 1 : 0;
 }
 
 int asw_census_cost16(const asw_params *p, const asw_census_params *cp, const uint8_t *left_rgba,
@@ -304,7 +311,7 @@ int asw_census_cost16(const asw_params *p, const asw_census_params *cp, const ui
                       void *stream) {
     ASW_CENSUS_CHECK(asw_census_params_check(p, cp));
     if (!left_rgba || !right_rgba || !cen_left || !cen_right || !cost) return ASW_E_INVALID;
-    if (!census16_exact(p, cp)) return ASW_E_UNSUPPORTED;
+    ASW_CENSUS_CHECK(census_cost16_check(p, cp));
     return launch_census_cost(true, p, cp, left_rgba, right_rgba, cen_left, cen_right, cost, stream);
 }
 

@@ -61,6 +61,15 @@ void note_pass_kernel(int dir, int dm, const char *kernel, int T, const char *sh
 // any allocation, and by every pass launch)
 int pass_shape_check(const asw_params *p);
 
+// ASW_OK when asw_raw_cost16 / asw_census_cost16 is built for p (and cp): the cost has a uint16
+// form (the tad_tau rule of include/asw.h) and the kernel's LDS stage holds the pitch; else
+// ASW_E_UNSUPPORTED.  The one rule of those entry points, asw_*16_supported and asw_set_sgm;
+// p (and cp) have passed their parameter checks.
+int raw_cost16_check(const asw_params *p);
+int census_cost16_check(const asw_params *p, const asw_census_params *cp);
+// ASW_OK when k_sgm_path is built for p's pitch (at most 65536 planes), else ASW_E_UNSUPPORTED
+int sgm_shape_check(const asw_params *p);
+
 // lane-per-pixel WTA scan (asw_refine.hip): mode 0 = asw_WTA, 1 = asw_WTA_REF
 // lane-per-pixel d-sharded WTA halves (ref = NULL: asw_WTA; else asw_WTA_REF's penalty)
 int launch_wta_local_scan(const asw_params *p, const float *cost, const float *ref, long long *key, float *m1,

@@ -103,6 +103,11 @@ struct asw_ctx {
     // asw_set_census: the census / AD-census cost in place of the AD raw cost
     asw_census_params cen{};
     bool census_on = false;
+    // asw_set_sgm: semi-global matching in place of the supports and the 2r passes: the raw
+    // cost as uint16 in shard 0's c1, asw_sgm's sums in its c0 (what the WTA onwards reads)
+    asw_sgm_params sgm{};
+    bool sgm_on = false;
+    void *sgm_ws = nullptr;
 };
 
 namespace {
@@ -333,7 +338,7 @@ int destroy_ctx(asw_ctx *c) {
     void *bufs[] = {c->red_tmp, c->d_ref, c->d_tar, c->conf_ref, c->conf_tar, c->code_ref, c->code_tar, c->lr,
                     c->lr_red, c->disp, c->disp16, c->lr16, c->rws, c->est, c->post_red, c->final_rgba,
                     c->nrws, c->n_est, c->n_dt, c->n_dr, c->n_post16, c->n_final16,
-                    c->sp_disp, c->sp_lr, c->sp_fill, c->cr_med_l, c->cr_med_r, c->cr_init, c->cr_final,
+                    c->sgm_ws, c->sp_disp, c->sp_lr, c->sp_fill, c->cr_med_l, c->cr_med_r, c->cr_init, c->cr_final,
                     c->cr_arms_l, c->cr_arms_r, c->cr_d0, c->cr_code0, c->cr_code1};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
@@ -435,6 +440,39 @@ int create_ctx(const asw_params *p, const int *devs, int n, int shard0, int tota
     }
     *out = c;
     return ASW_OK;
+}
+
+// whether the raw cost SGM reads is built: asw_raw_cost16's / asw_census_cost16's own rule
+bool cost16_exists(const asw_params *p, const asw_census_params *cen) {
+    return (cen ? asw::census_cost16_check(p, cen) : asw::raw_cost16_check(p)) == ASW_OK;
+}
+
+// asw_set_sgm on (one shard): the raw cost in its uint16 form into c1, asw_sgm's sums into c0.
+// No supports and no passes: taps and iters are not read.  The caller's next event (the WTA's
+// start) is the end of asw_timings.aggregation_total.
+int sgm_aggregate(asw_ctx *c, const uint8_t *left_rgba, const uint8_t *right_rgba, int e_raw, int e_pass0,
+                  bool timed) {
+    Shard &s = c->sh[0];
+    const asw_params *p = &s.p;
+    const size_t S = frame_pixels(p);
+    hipStream_t st = s.stream;
+    uint16_t *raw = reinterpret_cast<uint16_t *>(s.c1);
+    HIPCHK(hipSetDevice(s.device));
+    if (left_rgba) {
+        HIPCHK(hipMemcpyAsync(s.left, left_rgba, S * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(s.right, right_rgba, S * 4, hipMemcpyHostToDevice, st));
+    }
+    if (timed) HIPCHK(hipEventRecord(c->ev[e_raw], st));
+    if (c->census_on) {
+        ASWCHK(asw_census(p, &c->cen, s.left, s.cen_l, st));
+        ASWCHK(asw_census(p, &c->cen, s.right, s.cen_r, st));
+        ASWCHK(asw_census_cost16(p, &c->cen, s.left, s.right, s.cen_l, s.cen_r, raw, st));
+    } else {
+        ASWCHK(asw_raw_cost16(p, s.left, s.right, raw, st));
+    }
+    if (timed) HIPCHK(hipEventRecord(c->ev[e_raw + 1], st));
+    if (timed) HIPCHK(hipEventRecord(c->ev[e_pass0], st));
+    return asw_sgm(p, &c->sgm, raw, s.c0, c->sgm_ws, st);
 }
 
 // raw cost + supports + 2r passes of one shard, asynchronous on its stream.
@@ -619,7 +657,8 @@ int main_work_untimed(asw_ctx *c) {
     const size_t S = frame_pixels(p);
     Shard &s0 = c->sh[0];
     hipStream_t st = s0.stream;
-    ASWCHK(shard_aggregate(c, 0, nullptr, nullptr, 1, 3, false));
+    if (c->sgm_on) ASWCHK(sgm_aggregate(c, nullptr, nullptr, 1, 3, false));
+    else ASWCHK(shard_aggregate(c, 0, nullptr, nullptr, 1, 3, false));
     ASWCHK(single_wta(c));
     hipLaunchKernelGGL(k_codes_to_rgba, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, (long long)S,
                        c->code_ref, reinterpret_cast<uchar4 *>(c->disp));
@@ -822,7 +861,9 @@ int match_one(asw_ctx *c, const uint8_t *left_rgba, const uint8_t *right_rgba, a
         HIPCHK(hipEventRecord(ev[1], st));
         ASWCHK(graph_run(st, &c->g_main, &c->gx_main, [&] { return main_work_untimed(c); }));
     } else {
-        for (int i = 0; i < c->n; ++i) ASWCHK(shard_aggregate(c, i, left_rgba, right_rgba, 1, e_pass0));
+        if (c->sgm_on) ASWCHK(sgm_aggregate(c, left_rgba, right_rgba, 1, e_pass0, true));
+        else
+            for (int i = 0; i < c->n; ++i) ASWCHK(shard_aggregate(c, i, left_rgba, right_rgba, 1, e_pass0));
         if (c->comm == COMM_NONE) {
             HIPCHK(hipSetDevice(s0.device));
             HIPCHK(hipEventRecord(ev[e_x], st));
@@ -926,17 +967,23 @@ int match_one(asw_ctx *c, const uint8_t *left_rgba, const uint8_t *right_rgba, a
         std::memset(t, 0, sizeof(*t));
         t->h2d = ms_between(ev[0], ev[1]);
         t->raw_cost = ms_between(ev[1], ev[2]);
-        t->support = ms_between(ev[2], ev[e_pass0]);
-        double v = 0.0, h = 0.0;
-        for (int it = 0; it < r; ++it) {
-            v += ms_between(ev[e_pass0 + 2 * it], ev[e_pass0 + 2 * it + 1]);
-            h += ms_between(ev[e_pass0 + 2 * it + 1], ev[e_pass0 + 2 * it + 2]);
+        if (c->sgm_on) {  // no supports, no passes: the SGM launches, up to the WTA's start, are the aggregation
+            t->aggregation_total = ms_between(ev[e_pass0], ev[e_x]);
+        } else {
+            t->support = ms_between(ev[2], ev[e_pass0]);
+            double v = 0.0, h = 0.0;
+            for (int it = 0; it < r; ++it) {
+                v += ms_between(ev[e_pass0 + 2 * it], ev[e_pass0 + 2 * it + 1]);
+                h += ms_between(ev[e_pass0 + 2 * it + 1], ev[e_pass0 + 2 * it + 2]);
+            }
+            t->v_pass_mean = r ? v / r : 0.0;
+            t->h_pass_mean = r ? h / r : 0.0;
+            t->aggregation_total = ms_between(ev[e_pass0], ev[e_pass0 + 2 * r]);
         }
-        t->v_pass_mean = r ? v / r : 0.0;
-        t->h_pass_mean = r ? h / r : 0.0;
-        t->aggregation_total = ms_between(ev[e_pass0], ev[e_pass0 + 2 * r]);
         const bool sharded = c->comm != COMM_NONE;
-        t->exchange = sharded ? ms_between(ev[e_pass0 + 2 * r], ev[e_x]) : 0.0;
+        // (SGM on a one-rank asw_create_rank context records no pass marks: its WTA protocol,
+        // an exchange with no peer, is inside aggregation_total and both columns are 0)
+        t->exchange = sharded && !c->sgm_on ? ms_between(ev[e_pass0 + 2 * r], ev[e_x]) : 0.0;
         t->wta = sharded ? t->exchange : ms_between(ev[e_x], ev[e_wta]);
         t->consistency = ms_between(ev[e_wta], ev[c->sub_on ? e_sub : e_cons]);  // the sub-pixel maps: in no column
         t->total = ms_between(ev[1], ev[e_cons]);
@@ -1154,8 +1201,10 @@ int asw_set_cross(asw_ctx *c, const asw_cross_params *cp, const asw_cross_output
 
 int asw_set_census(asw_ctx *c, const asw_census_params *cp) {
     if (!c) return ASW_E_INVALID;
+    if (!cp && c->sgm_on && !cost16_exists(&c->p, nullptr)) return ASW_E_UNSUPPORTED;  // SGM reads the uint16 volume
     if (cp) {
         for (int i = 0; i < c->n; ++i) ASWCHK(asw_census_params_check(&c->sh[i].p, cp));
+        if (c->sgm_on && !cost16_exists(&c->p, cp)) return ASW_E_UNSUPPORTED;  // SGM reads the uint16 volume
         for (int i = 0; i < c->n; ++i) {
             Shard &s = c->sh[i];
             HIPCHK(hipSetDevice(s.device));
@@ -1168,6 +1217,35 @@ int asw_set_census(asw_ctx *c, const asw_census_params *cp) {
     }
     c->census_on = cp != nullptr;
     if (c->gx_main) {  // the captured frame holds the previous cost's launches: capture again
+        (void)hipGraphExecDestroy(c->gx_main);
+        (void)hipGraphDestroy(c->g_main);
+        c->gx_main = nullptr;
+        c->g_main = nullptr;
+    }
+    return ASW_OK;
+}
+
+int asw_set_sgm(asw_ctx *c, const asw_sgm_params *sp) {
+    if (!c) return ASW_E_INVALID;
+    if (sp) {
+        if (c->n > 1 || c->nranks > 1) return ASW_E_UNSUPPORTED;  // m is a minimum over every disparity
+        ASWCHK(asw_sgm_params_check(&c->sh[0].p, sp));
+        ASWCHK(asw::sgm_shape_check(&c->sh[0].p));
+        if (!cost16_exists(&c->p, c->census_on ? &c->cen : nullptr)) return ASW_E_UNSUPPORTED;
+        const size_t ws = asw_sgm_workspace_bytes(&c->sh[0].p, sp);
+        if (ws > 0) {
+            HIPCHK(hipSetDevice(c->sh[0].device));
+            void *buf = nullptr;
+            ASWCHK(dev_alloc(&buf, ws));
+            if (c->sgm_ws) (void)hipFree(c->sgm_ws);
+            c->sgm_ws = buf;
+        }
+        c->sgm = *sp;
+    } else if (!c->sgm_on) {
+        return ASW_OK;  // off already: nothing captured differs
+    }
+    c->sgm_on = sp != nullptr;
+    if (c->gx_main) {  // the captured frame holds the previous aggregator's launches: capture again
         (void)hipGraphExecDestroy(c->gx_main);
         (void)hipGraphDestroy(c->g_main);
         c->gx_main = nullptr;

@@ -594,11 +594,14 @@ size_t asw_lut_bytes(const asw_params *p) { return (size_t)(p->taps / 2 + 1) * k
         if (_s != ASW_OK) return _s;         \
     } while (0)
 
+// LDS stage of k_raw_cost for a pitch: 4 phases of s4 dwords
+static size_t raw_cost_lds(int Dp) { return (size_t)4 * (((kRawSpan + Dp - 1 + 3) / 4 + 31) / 32 * 32 + 8) * 4; }
+
 static int launch_raw_cost(bool u16, const asw_params *p, const uint8_t *left, const uint8_t *right, void *cost,
                            void *stream) {
     const int Dp = asw_disp_pitch(p);
     const dim3 grid((unsigned)((p->width + kRawSpan - 1) / kRawSpan), (unsigned)p->height);
-    const size_t lds = (size_t)4 * (((kRawSpan + Dp - 1 + 3) / 4 + 31) / 32 * 32 + 8) * 4;  // 4 phases of s4
+    const size_t lds = raw_cost_lds(Dp);
     if (lds > 64 * 1024) return ASW_E_UNSUPPORTED;
     const uchar4 *l = reinterpret_cast<const uchar4 *>(left), *r = reinterpret_cast<const uchar4 *>(right);
     if (u16)
@@ -622,13 +625,13 @@ static bool raw16_exact(const asw_params *p) { return p->tad_tau >= 765.0f || p-
 int asw_raw16_supported(const asw_params *p) {
     if (!p || asw_params_check(p) != ASW_OK) return 0;
     // exact, and read by a ring-kernel first V pass (asw_aggregate_pass_den16)
-    return raw16_exact(p) && p->tad_tau >= 0.0f && p->iters >= 1 && asw::ring_taps(p->taps) ? 1 : 0;
+    return asw::raw_cost16_check(p) == ASW_OK && p->iters >= 1 && asw::ring_taps(p->taps) ? 1 : 0;
 }
 
 int asw_raw_cost16(const asw_params *p, const uint8_t *left, const uint8_t *right, uint16_t *cost, void *stream) {
     ASW_CHECK_PARAMS(p);
     if (!left || !right || !cost) return ASW_E_INVALID;
-    if (!raw16_exact(p) || p->tad_tau < 0.0f) return ASW_E_UNSUPPORTED;
+    if (const int s = asw::raw_cost16_check(p)) return s;
     return launch_raw_cost(true, p, left, right, cost, stream);
 }
 
@@ -856,3 +859,10 @@ int asw_consistency(const asw_params *p, const int32_t *d_ref, const int32_t *d_
 }
 
 }  // extern "C"
+
+namespace asw {
+int raw_cost16_check(const asw_params *p) {
+    if (!raw16_exact(p) || p->tad_tau < 0.0f) return ASW_E_UNSUPPORTED;
+    return raw_cost_lds(asw_disp_pitch(p)) > 64 * 1024 ? ASW_E_UNSUPPORTED : ASW_OK;
+}
+}  // namespace asw

@@ -42,7 +42,11 @@
 //   * --census replaces the AD raw cost by the census / AD-census cost (asw_set_census;
 //     --census-win WxH, --census-weights A,C: w_a * min(AD, tau) + w_c * hamming, A = 0 is
 //     census only).  The outputs and the TSV columns are unchanged; the `aggr` column then
-//     holds the time of the two transforms and the census cost.
+//     holds the time of the two transforms and the census cost;
+//   * --sgm aggregates by semi-global matching (asw_set_sgm; --sgm-paths 4|8,
+//     --sgm-penalties P1,P2) in place of the supports and the ASW passes: --taps and --iters
+//     are then not read.  The outputs and the TSV columns are unchanged; `total aggregation`
+//     then holds the SGM launches, supp_w and the two pass means are 0.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -69,6 +73,9 @@ struct Options {
     int cross_arm = -1, cross_tau = -1;
     bool census = false;  // --census: the census / AD-census cost (asw_set_census)
     int census_w = -1, census_h = -1, census_ad = -1, census_wc = -1;
+    bool sgm = false;  // --sgm: semi-global matching in place of the ASW passes (asw_set_sgm)
+    bool sgm_paths_given = false, sgm_penalties_given = false;  // any integer reaches asw_set_sgm
+    int sgm_paths = 0, sgm_p1 = 0, sgm_p2 = 0;
 };
 
 void usage() {
@@ -78,12 +85,16 @@ void usage() {
                  "                  [--refine K] [--device I | --devices I,J,...] [--png16] [--tsv FILE]\n"
                  "                  [--subpixel] [--cross [--cross-arm N] [--cross-tau N]]\n"
                  "                  [--census [--census-win WxH] [--census-weights A,C]]\n"
+                 "                  [--sgm [--sgm-paths 4|8] [--sgm-penalties P1,P2]]\n"
                  "  --refine K  refinement iterations + 3x3 median (default 6, 0 = off): asw_disparity.png and\n"
                  "              asw_consistency_post-reff.png; with --ndisp > 256 or --native-lr the loop runs on disparity\n"
                  "              indices and writes asw_disparity16.png and asw_consistency_post16.png (65535 = inconsistent)\n"
                  "  --census    the census / AD-census cost A * min(AD, tau) + C * hamming in place of the AD raw cost\n"
                  "              (robust to a gain / offset between the views); window W, H in 3, 5, 7, 9 but 9x9\n"
                  "              (default 9x7), weights A 0..64, C 1..1024 (default 1,8; A = 0: census only)\n"
+                 "  --sgm       semi-global matching on the integer raw cost in place of the supports and the ASW passes\n"
+                 "              (--taps and --iters are not read): 4 or 8 paths (default 8), penalties\n"
+                 "              0 <= P1 <= P2 <= 1048576 (default 16,128); one GPU\n"
                  "  --cross     the reference's cross-based matcher first (one GPU, --ndisp <= 256): cross_based_initial.png,\n"
                  "              cross_based_disparity.png, median.png, and its timing columns in front of the ASW columns of the TSV\n"
                  "  --subpixel  float sub-pixel disparity (needs --ndisp <= 1024): asw_disparity_sub.pfm (LR-masked,\n"
@@ -139,6 +150,19 @@ bool parse(int argc, char **argv, Options &o) {
             if (!(v = next("--census-weights"))) return false;
             if (std::sscanf(v, "%d,%d", &o.census_ad, &o.census_wc) != 2) return false;
             o.census = true;
+        }
+        else if (a == "--sgm") o.sgm = true;
+        else if (a == "--sgm-paths") {
+            if (!(v = next("--sgm-paths"))) return false;
+            char tail = 0;
+            if (std::sscanf(v, "%d%c", &o.sgm_paths, &tail) != 1) return false;
+            o.sgm = o.sgm_paths_given = true;
+        }
+        else if (a == "--sgm-penalties") {
+            if (!(v = next("--sgm-penalties"))) return false;
+            char tail = 0;
+            if (std::sscanf(v, "%d,%d%c", &o.sgm_p1, &o.sgm_p2, &tail) != 2) return false;
+            o.sgm = o.sgm_penalties_given = true;
         }
         else if (a == "--lab") o.lab = true;
         else if (a == "--no-lr") o.lr = false;
@@ -292,6 +316,19 @@ int main(int argc, char **argv) {
             st = asw_set_census(ctx, &np);
             if (st != ASW_OK) {
                 std::fprintf(stderr, "%s: asw_set_census: %s\n", folder.c_str(), asw_strerror(st));
+                ++failures;
+                asw_destroy(ctx);
+                continue;
+            }
+        }
+        if (o.sgm) {  // after the census switch: the check needs the cost SGM will read
+            asw_sgm_params sp;
+            asw_sgm_params_default(&sp);
+            if (o.sgm_paths_given) sp.paths = o.sgm_paths;
+            if (o.sgm_penalties_given) sp.p1 = o.sgm_p1, sp.p2 = o.sgm_p2;
+            st = asw_set_sgm(ctx, &sp);
+            if (st != ASW_OK) {
+                std::fprintf(stderr, "%s: asw_set_sgm: %s\n", folder.c_str(), asw_strerror(st));
                 ++failures;
                 asw_destroy(ctx);
                 continue;

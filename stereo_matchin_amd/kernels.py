@@ -172,6 +172,43 @@ def census16_supported(p: AswParams, cp) -> bool:
     return bool(_lib.lib().asw_census16_supported(ctypes.byref(p), ctypes.byref(cp)))
 
 
+# ------------------------------------------------------- semi-global matching
+# No reference counterpart (its only aggregator is the ASW pass): include/asw.h §SGM.
+
+def _sgm_volumes(p: AswParams, cost16, out):
+    _expect(cost16, cost_shape(p), torch.int16, "cost16")
+    if out is None:
+        out = torch.empty(cost_shape(p), dtype=torch.float32, device=cost16.device)
+    _expect(out, cost_shape(p), torch.float32, "out")
+    return out
+
+
+def sgm_path(p: AswParams, sp, k: int, cost16: torch.Tensor, out: torch.Tensor | None = None,
+             accumulate: bool = False) -> torch.Tensor:
+    """asw_sgm_path: the path costs L_k of the uint16 raw costs (int16 storage [H][W][Dp]),
+    written to ``out`` (float32 [H][W][Dp], padding planes +0) or, with ``accumulate``, added
+    to it."""
+    if accumulate and out is None:
+        raise ValueError("sgm_path: accumulate needs the volume to add to (out)")
+    out = _sgm_volumes(p, cost16, out)
+    _lib.check(_lib.lib().asw_sgm_path(ctypes.byref(p), ctypes.byref(sp), k, _ptr(cost16), _ptr(out),
+                                       1 if accumulate else 0, _stream(cost16.device)), "asw_sgm_path")
+    return out
+
+
+def sgm(p: AswParams, sp, cost16: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """asw_sgm: the sum over ``sp.paths`` paths of the path costs, float32 [H][W][Dp]
+    (integers below 2^24, exact), padding planes +0."""
+    out = _sgm_volumes(p, cost16, out)
+    L = _lib.lib()
+    _lib.check(L.asw_sgm_params_check(ctypes.byref(p), ctypes.byref(sp)), "asw_sgm_params_check")
+    n = int(L.asw_sgm_workspace_bytes(ctypes.byref(p), ctypes.byref(sp)))
+    ws = torch.empty(n, dtype=torch.uint8, device=cost16.device) if n else None
+    _lib.check(L.asw_sgm(ctypes.byref(p), ctypes.byref(sp), _ptr(cost16), _ptr(out), _ptr(ws),
+                         _stream(cost16.device)), "asw_sgm")
+    return out
+
+
 def support_lut(p: AswParams, device, out: torch.Tensor | None = None) -> torch.Tensor:
     """(R+1) x 766 table of exp(-sad/gamma_c - dist/gamma_g) (K/asw_vsupport.cl:22-25)."""
     if out is None:

@@ -54,9 +54,14 @@ class StereoMatcher:
 
     ``census``: None (the AD raw cost), True (the default AD-census cost) or an
     AswCensusParams: ``raw_and_support`` then runs asw_census on both images and the census
-    cost in place of asw_Aggr (include/asw.h §census)."""
+    cost in place of asw_Aggr (include/asw.h §census).
 
-    def __init__(self, params: AswParams, device="cuda", den_cache: bool = True, census=None):
+    ``sgm``: None (the ASW passes), True (8 paths, P1 16, P2 128) or an AswSgmParams:
+    semi-global matching (asw_sgm) on the uint16 raw cost in place of the supports and the
+    passes; ``taps`` and ``iters`` are then not read and no support array is allocated
+    (include/asw.h §SGM)."""
+
+    def __init__(self, params: AswParams, device="cuda", den_cache: bool = True, census=None, sgm=None):
         st = _lib.params_check(params)
         if st != _lib.ASW_OK:
             raise _lib.AswError(st, "asw_params_check")
@@ -65,8 +70,26 @@ class StereoMatcher:
         if self.census is not None:
             _lib.check(_lib.lib().asw_census_params_check(ctypes.byref(self.p), ctypes.byref(self.census)),
                        "asw_census_params_check")
+        self.sgm = _lib.sgm_params_of(sgm)
         self.device = torch.device(device)
         dev = self.device
+        self.local = None
+        if self.sgm is not None:
+            _lib.check(_lib.lib().asw_sgm_params_check(ctypes.byref(self.p), ctypes.byref(self.sgm)),
+                       "asw_sgm_params_check")
+            self.cen_l = self.cen_r = None
+            if self.census is not None:
+                self.cen_l = torch.empty((self.p.height, self.p.width), dtype=torch.int64, device=dev)
+                self.cen_r = torch.empty_like(self.cen_l)
+            # the raw cost as uint16 in c1's first half, the sums in c0 (what match() reads on)
+            self.c0 = K.new_cost(self.p, dev)
+            self.c1 = K.new_cost(self.p, dev)
+            self.raw16 = True
+            self.c1_16 = K.cost16_view(self.c1)
+            # what only the supports and the passes use
+            self.lut = self.wvl = self.wvr = self.whl = self.whr = None
+            self.c0_16 = self.den_v = self.den_h = None
+            return
         self.lut = torch.empty(K.lut_shape(self.p), dtype=torch.float32, device=dev)
         self.wvl, self.wvr, self.whl, self.whr = (K.new_support(self.p, dev) for _ in range(4))
         self.c0 = K.new_cost(self.p, dev)
@@ -94,8 +117,17 @@ class StereoMatcher:
 
     # -- stages ---------------------------------------------------------------
     def raw_and_support(self, left: torch.Tensor, right: torch.Tensor):
-        """asw_Aggr (or the census cost) into c0 and the four support arrays."""
+        """asw_Aggr (or the census cost) into c0 and the four support arrays; with SGM on
+        the uint16 raw cost into c1 alone."""
         p = self.p
+        if self.sgm is not None:
+            if self.census is not None:
+                K.census(p, self.census, left, out=self.cen_l)
+                K.census(p, self.census, right, out=self.cen_r)
+                K.census_cost16(p, self.census, left, right, self.cen_l, self.cen_r, out=self.c1_16)
+            else:
+                K.asw_Aggr16(p, left, right, out=self.c1_16)
+            return
         if self.census is not None:
             cp = self.census
             K.census(p, cp, left, out=self.cen_l)
@@ -123,6 +155,11 @@ class StereoMatcher:
         """r x (V: c0 -> c1, H: c1 -> c0); the result is in c0 (main.cpp:486-515)."""
         p = self.p
         self.local = None
+        if self.sgm is not None:  # asw_sgm: c1 (uint16 raw cost) -> c0
+            K.sgm(p, self.sgm, self.c1_16, out=self.c0)
+            if events is not None:
+                events.append(("sgm", _record()))
+            return self.c0
         for it in range(p.iters):
             dmv = _lib.DEN_NONE if self.den_v is None else (_lib.DEN_WRITE if it == 0 else _lib.DEN_READ)
             dm = _lib.DEN_NONE if self.den_h is None else (_lib.DEN_WRITE if it == 0 else _lib.DEN_READ)
@@ -266,7 +303,7 @@ class FrameContext:
     """
 
     def __init__(self, params: AswParams, devices=(0,), rank: int | None = None, nranks: int | None = None,
-                 comm_id: bytes | None = None, refine=None, graph: bool = False, census=None):
+                 comm_id: bytes | None = None, refine=None, graph: bool = False, census=None, sgm=None):
         self.L = _lib.lib()
         self.p = params.copy()
         self.ctx = ctypes.c_void_p()
@@ -303,6 +340,18 @@ class FrameContext:
         self.census = None
         if census is not None and census is not False:
             self.set_census(census)
+        self.sgm = None
+        if sgm is not None and sgm is not False:
+            self.set_sgm(sgm)
+
+    def set_sgm(self, sgm=True) -> None:
+        """``asw_set_sgm``: semi-global matching (asw_sgm) on the uint16 raw cost in place of
+        the supports and the ASW passes of every later match.  ``sgm``: an AswSgmParams, True
+        for the defaults (8 paths, P1 16, P2 128), None / False to turn it off again.
+        One-shard contexts whose cost has a uint16 form (else ASW_E_UNSUPPORTED)."""
+        sp = _lib.sgm_params_of(sgm)
+        _lib.check(self.L.asw_set_sgm(self.ctx, ctypes.byref(sp) if sp is not None else None), "asw_set_sgm")
+        self.sgm = sp
 
     def set_census(self, census=True) -> None:
         """``asw_set_census``: the census / AD-census cost in place of the AD raw cost of every
@@ -451,8 +500,9 @@ def comm_unique_id() -> bytes:
 
 
 def match_frame(params: AswParams, left_rgba: np.ndarray, right_rgba: np.ndarray, device: int = 0,
-                want_cost: bool = False, refine=None, devices=None, want16: bool = False, census=None) -> dict:
+                want_cost: bool = False, refine=None, devices=None, want16: bool = False, census=None,
+                sgm=None) -> dict:
     """Frame API (``asw_create`` + ``asw_match``): host RGBA8 in, host maps out."""
     with FrameContext(params, devices=devices if devices is not None else (device,), refine=refine,
-                      census=census) as fc:
+                      census=census, sgm=sgm) as fc:
         return fc.match(left_rgba, right_rgba, want_cost=want_cost, want16=want16)
