@@ -201,7 +201,9 @@ int asw_census16_supported(const asw_params *p, const asw_census_params *cp);
  * asw_sgm_params_check: ASW_E_INVALID for paths not 4 or 8, penalties outside
  * 0 <= p1 <= p2 <= 1048576, a p that fails asw_params_check, or a shard p (d_begin > 0 or
  * d_end < ndisp: m is a minimum over every disparity).  Offsets are 64-bit: no accepted shape
- * overflows them (a pitch above 65536 planes is ASW_E_UNSUPPORTED at launch).
+ * overflows them (a pitch above 65536 planes is ASW_E_UNSUPPORTED at launch, and so is a shape
+ * whose walkers, max(width, height) blocks of up to 1024 threads at pitches above 256, exceed
+ * the 2^32 - 1 work-items of a launch: e.g. height 2^22 at 4096 planes).
  *   asw_sgm_path: path k alone (0 <= k < 8 whatever sp->paths, else ASW_E_INVALID).
  *     accumulate == 0: sum = (float)L_k on the valid planes, +0 on the padding planes;
  *     accumulate != 0: sum = sum + (float)L_k on the valid planes, padding planes kept.
@@ -226,7 +228,9 @@ int asw_support_lut(const asw_params *p, float *lut, void *stream);
 /* replaces asw_vSupport / asw_hSupport (K/asw_vsupport.cl:3-27, K/asw_hsupport.cl:3-28),
  * launched at main.cpp:469-484 (once per image and direction).  RGB contexts only
  * (ASW_E_INVALID for ASW_COLOR_LAB: use asw_lab + asw_support_lab).  The padding taps
- * i >= taps of every pixel are written 0 (asw_support_all and asw_support_lab too). */
+ * i >= taps of every pixel are written 0 (asw_support_all and asw_support_lab too).
+ * A row of width * Tp floats is indexed in 32 bits: width * Tp + 255 > 2^31 - 1 is
+ * ASW_E_UNSUPPORTED in all three entry points (no kernel is launched). */
 int asw_support(const asw_params *p, int dir, const uint8_t *img_rgba, const float *lut, float *w,
                 void *stream);
 
@@ -282,7 +286,11 @@ int asw_aggregate_den(const asw_params *p, const float *wvl, const float *wvr, c
 
 /* replaces asw_WTA (K/asw_wta.cl:12-82), launched at main.cpp:517-526, for a context
  * that owns the whole disparity range: left first-argmin + confidence, the
- * bresenham target scan, and the 8-bit codes the reference writes to its images. */
+ * bresenham target scan, and the 8-bit codes the reference writes to its images.
+ * The target scan (here, in asw_wta_target_local, asw_wta_ref and asw_wta_ref_target_local)
+ * gathers with 32-bit byte offsets from the start of a row: (width + 64) * Dp * 4 >= 2^31
+ * is ASW_E_UNSUPPORTED (no kernel is launched); asw_wta through the row sweep
+ * (ASW_TUNE_WTA_VARIANT 2, Dp 64 / 128 / 256) has no such limit. */
 int asw_wta(const asw_params *p, const float *cost, int32_t *d_ref, float *conf_ref, int32_t *d_tar,
             float *conf_tar, uint8_t *code_ref, uint8_t *code_tar, void *stream);
 
@@ -458,7 +466,11 @@ int asw_refine_native(const asw_params *p, const asw_refine_params *rp, const ui
  * p only (d_begin = 0, d_end = ndisp) with 2 <= ndisp <= 256 (8-bit codes); reads width,
  * height and ndisp of p.  Volumes are [H][W][Dp] float32 like every cost volume; an arm
  * map is [H][W] of four signed bytes (h-, h+, v-, v+) = (-a, +a, -a, +a), a in
- * [1, arm_max] (the reference: four int planes). */
+ * [1, arm_max] (the reference: four int planes).  The volume stages launch one work-item per
+ * element (asw_cross_cost, asw_cross_oii) or one wave per 64 planes of a line
+ * (asw_cross_integral); a launch holds at most 2^32 - 1 work-items, so width * height * Dp
+ * >= 2^32 - 255 elements (or, for the integral, lines * Dp >= 2^32 - 255) is
+ * ASW_E_UNSUPPORTED (no kernel is launched). */
 typedef struct asw_cross_params {
     int arm_max; /* longest arm (K/cross.cl:32-80: 25), 1..127                            */
     int tau;     /* colour similarity in 8-bit units, 0..255: 25 is exactly the reference's

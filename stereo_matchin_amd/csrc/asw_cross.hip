@@ -294,10 +294,13 @@ inline int cross_shape_check(const asw_params *p) {
 
 inline dim3 row_grid(const asw_params *p) { return dim3((unsigned)((p->width + 255) / 256), (unsigned)p->height); }
 
-// blocks of 256 threads over n items; ASW_E_UNSUPPORTED past the grid limit
+// blocks of kFlatThreads threads over n items; ASW_E_UNSUPPORTED past the grid limit: a
+// dispatch holds its work-item count per dimension in 32 bits, so blocks * kFlatThreads
+// must stay below 2^32 (a launch past it fails, it never runs with a wrapped grid)
+constexpr long long kFlatThreads = 256;
 inline int flat_grid(long long n, long long per_block, dim3 *g) {
     const long long blocks = (n + per_block - 1) / per_block;
-    if (blocks > 0x7fffffffLL) return ASW_E_UNSUPPORTED;
+    if (blocks * kFlatThreads > 0xffffffffLL) return ASW_E_UNSUPPORTED;
     *g = dim3((unsigned)blocks);
     return ASW_OK;
 }

@@ -645,8 +645,15 @@ int asw_support_lut(const asw_params *p, float *lut, void *stream) {
     return finish_launch();
 }
 
+// the support kernels index a row's W * Tp floats (and the image's W * H pixels) in 32 bits,
+// and their launchers round that count up to whole blocks of 256 in 32 bits too
+static int support_shape_check(const asw_params *p) {
+    return (long long)p->width * asw_tap_pitch(p) + 255 > INT_MAX ? ASW_E_UNSUPPORTED : ASW_OK;
+}
+
 static int launch_support(const asw_params *p, const SupportJobs &jobs, int njobs, const float *lut, void *stream) {
     const hipStream_t st = (hipStream_t)stream;
+    if (const int s = support_shape_check(p)) return s;
     switch (asw_tap_pitch(p) / 4) {  // Tp = 4Q, Q odd past 1 (tap_pitch)
         case 1: launch_support_q<1>(p, jobs, njobs, lut, st); break;
         case 3: launch_support_q<3>(p, jobs, njobs, lut, st); break;
@@ -707,6 +714,7 @@ int asw_support_lab(const asw_params *p, int dir, const float *lab, float *w, vo
     ASW_CHECK_PARAMS(p);
     if (!lab || !w || (dir != ASW_DIR_V && dir != ASW_DIR_H)) return ASW_E_INVALID;
     if (p->color_space != ASW_COLOR_LAB) return ASW_E_INVALID;
+    if (const int s = support_shape_check(p)) return s;
     const int Tp = asw_tap_pitch(p);
     const dim3 grid((unsigned)((p->width * Tp + 255) / 256), (unsigned)p->height);
     hipLaunchKernelGGL(k_support_lab, grid, dim3(256), 0, (hipStream_t)stream,

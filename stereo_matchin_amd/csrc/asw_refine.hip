@@ -155,8 +155,11 @@ __device__ __forceinline__ void target_scan_skewed(const float *__restrict__ cos
     const long long vol_left = (S - y0W) * Dp * 4;
     const rsrc_t rsc = make_rsrc_n(cost + y0W * Dp, vol_left < 0x7fffffffLL ? (int)vol_left : 0x7fffffff);
     const int lanepix = (int)(pc - y0W);
-    const int stride = (Dp + 1) * 4;
-    const int A = (lanepix * Dp + md - b_lo) * 4 + skew * stride;
+    // A and (j+k)*stride can pass 2^31 (a deep range, a row near the limit of
+    // wta_target_shape_check) although their difference, the offset, never does: they are
+    // formed in unsigned arithmetic, which is modular by definition
+    const unsigned stride = (unsigned)(Dp + 1) * 4u;
+    const unsigned A = ((unsigned)lanepix * (unsigned)Dp + (unsigned)(md - b_lo)) * 4u + (unsigned)skew * stride;
     const int flo = ((lanepix - x) * Dp + md - x - b_lo) * 4;
     cur_t = kSentinel;
     last_t = kSentinel;
@@ -172,7 +175,7 @@ __device__ __forceinline__ void target_scan_skewed(const float *__restrict__ cos
             // (profiles/r03/wta_probe_r08j.log); the others keep +inf
             const int i = j + k - skew;
             tv[k] = __builtin_inff();
-            if ((unsigned)(i - i_lo) < (unsigned)ilen) tv[k] = bload(rsc, max(A - (j + k) * stride, flo));
+            if ((unsigned)(i - i_lo) < (unsigned)ilen) tv[k] = bload(rsc, max((int)(A - (unsigned)(j + k) * stride), flo));
         }
 #pragma unroll
         for (int k = 0; k < kGather; ++k) {
@@ -427,6 +430,15 @@ inline void scan_grid(const asw_params *p, int &nwaves, int &per_xcd, unsigned &
 }
 }  // namespace
 
+// target_scan_skewed addresses a wave's gathers with 32-bit byte offsets from the start of
+// the wave's first row, inside a buffer of at most 2^31 - 1 bytes: the wave's last pixel lies
+// up to W + 62 pixels past that start, so one row plus 64 pixels must stay below 2 GiB
+// (DESIGN.md §Far addressing).  The own scan and the row sweep use 64-bit offsets.
+static int wta_target_shape_check(const asw_params *p) {
+    const long long reach = ((long long)p->width + 64) * asw_disp_pitch(p) * 4;
+    return reach >= (1LL << 31) ? ASW_E_UNSUPPORTED : ASW_OK;
+}
+
 int launch_wta_local_scan(const asw_params *p, const float *cost, const float *ref, long long *key, float *m1,
                           float *m2, hipStream_t st) {
     int nwaves, per_xcd;
@@ -444,6 +456,7 @@ int launch_wta_local_scan(const asw_params *p, const float *cost, const float *r
 
 int launch_wta_target_local_scan(const asw_params *p, const float *cost, const long long *key_ref, const float *ref,
                                  long long *tkey, float *t1, float *t2, hipStream_t st) {
+    if (const int s = wta_target_shape_check(p)) return s;
     int nwaves, per_xcd;
     unsigned nb;
     scan_grid(p, nwaves, per_xcd, nb);
@@ -460,6 +473,7 @@ int launch_wta_target_local_scan(const asw_params *p, const float *cost, const l
 int launch_wta_scan(const asw_params *p, int mode, const float *cost, const float *ref_l, const float *ref_r,
                     int32_t *d_ref, float *conf_ref, int32_t *d_tar, float *conf_tar, uint8_t *code_ref,
                     uint8_t *code_tar, hipStream_t st) {
+    if (const int s = wta_target_shape_check(p)) return s;
     const long long S = (long long)p->width * p->height;
     const int nwaves = (int)((S + 63) / 64);
     const int per_xcd = ((nwaves + 3) / 4 + 7) / 8;  // blocks of 4 waves per XCD, the grid is exactly 8 x per_xcd

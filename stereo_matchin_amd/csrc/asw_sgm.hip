@@ -339,8 +339,20 @@ int launch_path(const asw_params *p, const asw_sgm_params *sp, int k, const uint
 
 }  // namespace
 
+// threads of a walker at a pitch (launch_path's forms)
+static int sgm_threads(int Dp) {
+    if (Dp <= 256) return 64;
+    const int PL = Dp <= 4 * 64 * kSgmMaxWaves ? 4 : Dp <= 16 * 64 * kSgmMaxWaves ? 16 : Dp <= 32 * 64 * kSgmMaxWaves ? 32 : 64;
+    return round_up((Dp + PL - 1) / PL, 64);
+}
+
+// a pitch k_sgm_path is built for, and launches (one block per row or per column) of at
+// most 2^32 - 1 work-items, what a dispatch holds
 int sgm_shape_check(const asw_params *p) {
-    return asw_disp_pitch(p) <= 64 * 64 * kSgmMaxWaves ? ASW_OK : ASW_E_UNSUPPORTED;
+    const int Dp = asw_disp_pitch(p);
+    if (Dp > 64 * 64 * kSgmMaxWaves) return ASW_E_UNSUPPORTED;
+    const long long walkers = p->width > p->height ? p->width : p->height;
+    return walkers * sgm_threads(Dp) > 0xffffffffLL ? ASW_E_UNSUPPORTED : ASW_OK;
 }
 
 }  // namespace asw
