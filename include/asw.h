@@ -520,7 +520,11 @@ int asw_cross_vote(const asw_params *p, const uint8_t *code0, const int8_t *arms
 /* tuning hook (benchmarks / kernel experiments): selects among compiled kernel
  * variants; returns the previous value, or ASW_E_INVALID for an unknown key.
  * Every variant computes bit-identical results. */
-#define ASW_TUNE_PASS_VARIANT 1
+#define ASW_TUNE_PASS_VARIANT 1 /* aggregation passes, a bit set: 128 H by k_hpass9, 4096 H by k_hpass11 at any
+                                  frame size, 0xF00 k_hpass11's segment length in window periods; bit 26 flips the
+                                  cache policy of the cost / den / output streams (nt from 256 MiB of volume on)
+                                  in the 64-lane V passes, k_hpass9 and the 32-plane passes (k_hpass11 is nt
+                                  always); bits 16-23 the 32-plane passes' strip / segment counts */
 #define ASW_TUNE_WTA_VARIANT 2 /* asw_wta: 0 lane-per-pixel scan (default), 2 row sweep (Dp 64/128/256; the
                                   scan elsewhere); 1 (round 1's wave per pixel) is no longer built */
 int asw_tune_set(int key, int value);

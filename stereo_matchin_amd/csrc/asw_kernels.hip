@@ -507,8 +507,8 @@ int asw_tune_set(int key, int value) {
     if (key == ASW_TUNE_PASS_VARIANT) {
         // only bits that select a compiled form (launch_dm): a stale bit would time the
         // default kernel under another name
-        // (+ bits 16-23: strip / segment counts, and bit 26: the nt policy flip of the
-        // 32-plane shard passes, asw_pass32.h)
+        // (+ bits 16-23: strip / segment counts of the 32-plane shard passes, asw_pass32.h,
+        // and bit 26: the nt policy flip of every pass but k_hpass11, which is nt always)
         if (value & ~(asw::kPassVariantBits | 0xFF0000 | (1 << 26))) return ASW_E_INVALID;
         return asw::set_pass_variant(value);
     }

@@ -581,6 +581,12 @@ template <int T, int NWB, int DM, int CP, int NPH, bool RING16 = true, int WPE =
           int PX = 0>
 void launch_h32(const asw_params *p, const float *wl, const float *wr, const float *cin, float *cout, float *den,
                 hipStream_t st, int seg_len) {
+#ifndef ASW_PASS_EXP_FORMS  // (tools/exp builds other forms and records no name)
+    // the name reported below says what ran: the labels hold for these forms only
+    static_assert(!DL || (NWB == 1 && NPH == 4), "the DL label names the 1-wave, 4-phase form");
+    static_assert(PX == 0 || (DL && PX == 8), "the PX=8 label names the DL form with PX = 8");
+    static_assert(DL || NWB == 4 || NWB == 2, "no label for this block shape");
+#endif
     const int W = p->width, H = p->height;
     const int nseg = (W + seg_len - 1) / seg_len;
     const int npairs = (H + 1) / 2 * nseg;  // work items: (row pair, segment)

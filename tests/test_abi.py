@@ -37,7 +37,7 @@ def test_tune_set_rejects_bits_that_select_nothing(L):
     lib = L.lib()
     assert lib.asw_tune_set(1, 64) == L.ASW_E_INVALID      # round 1's 10-wave H form: no longer built
     assert lib.asw_tune_set(1, 1 << 28) == L.ASW_E_INVALID
-    assert lib.asw_tune_set(1, 1 << 26) == 0 and lib.asw_tune_set(1, 0) == 1 << 26  # 32-plane passes: nt flipped
+    assert lib.asw_tune_set(1, 1 << 26) == 0 and lib.asw_tune_set(1, 0) == 1 << 26  # the passes' nt policy flipped
     # round 6: the 32-plane H pass's 4-wave-block (bit 24) and LDS-left-ring (bit 27) forms are no longer built
     assert lib.asw_tune_set(1, 1 << 24) == L.ASW_E_INVALID
     assert lib.asw_tune_set(1, 1 << 27) == L.ASW_E_INVALID

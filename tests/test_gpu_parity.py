@@ -205,7 +205,7 @@ def test_den_cache_write_then_read(gpu, oracle, T, direction, H, W, D, d0, d1):
 # the uint16 volume holds exactly asw_raw_cost's floats, and the pass equals the float
 # pass bit for bit (64-lane k_vpass10 and, for a shard of <= 32 planes, k_vpass32),
 # incl. padding planes, truncated AD at an integral tau, both den modes
-@pytest.mark.parametrize("T", [5, 9, 33, 35, 51])
+@pytest.mark.parametrize("T", [3, 5, 7, 9, 15, 33, 35, 51])  # every ring tap count
 @pytest.mark.parametrize("H,W,D,d0,d1,tau", [(37, 91, 70, 0, 70, 765.0), (23, 150, 200, 70, 135, 765.0),
                                               (40, 77, 64, 0, 64, 90.0), (3, 5, 9, 0, 9, 765.0),
                                               (150, 70, 64, 0, 64, 765.0), (233, 37, 200, 10, 140, 90.0),
