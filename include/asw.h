@@ -103,7 +103,10 @@ int asw_last_hip_error(void); /* hipError_t of the last ASW_E_HIP */
  *      asw_median3_u16, asw_refine_native) and asw_set_refine_native with its own
  *      asw_refine_native_outputs struct; the semi-global matching aggregator (asw_sgm_params_default,
  *      asw_sgm_params_check, asw_sgm_workspace_bytes, asw_sgm_path, asw_sgm) and asw_set_sgm with
- *      its own asw_sgm_params struct. */
+ *      its own asw_sgm_params struct; the speckle filter (asw_speckle_params_default,
+ *      asw_speckle_params_check, asw_speckle_workspace_bytes, asw_lr_valid, asw_speckle,
+ *      asw_speckle_mask16, asw_speckle_mask_f32) and asw_set_speckle with its own asw_speckle_params
+ *      and asw_speckle_outputs structs. */
 #define ASW_ABI_VERSION 4
 int asw_abi_version(void);
 
@@ -345,6 +348,48 @@ int asw_disp_mask(const asw_params *p, const float *disp, const int32_t *d_ref, 
  * one that exists at a row end, 0.0f in a row without a valid pixel).  The output holds
  * no NaN.  disp_lr != disp_filled. */
 int asw_disp_fill(const asw_params *p, const float *disp_lr, float *disp_filled, void *stream);
+
+/* ---- speckle filter: connected components of similar disparity (no reference counterpart;
+ * the post-filter of OpenCV's filterSpeckles and Hirschmueller's peak filter).  Integers only,
+ * free of any order.  Input: d, int32 [H][W], any values; valid, uint8
+ * [H][W], non-zero = valid, NULL = every pixel valid.  Pixels p and q are LINKED when they are
+ * 4-neighbours, both valid and |d[p] - d[q]| <= max_diff (the difference in 64 bits: INT32_MIN
+ * beside INT32_MAX is not linked).  A component is a connected component of that graph (a ramp
+ * 0, 1, 2, ... is one component at max_diff 1).  Every element of every output is written:
+ *   valid p:    label[p] = the smallest flat index y*W + x of p's component,
+ *               size[p]  = the component's pixel count, keep[p] = size[p] >= min_size
+ *   invalid p:  label[p] = -1, size[p] = 0, keep[p] = 0
+ * asw_speckle_params_check: ASW_E_UNSUPPORTED for width * height > 2^31 - 1 (labels are int32
+ * pixel indices; nothing is launched; checked first, since asw_params_check has a pixel limit of
+ * its own, 2^25 today, and answers ASW_E_INVALID); ASW_E_INVALID for min_size < 1, max_diff
+ * outside 0..65535 or a p that fails asw_params_check.  Only width and height of p are read: a
+ * shard p and any ndisp are fine.
+ *   asw_speckle: label, size and keep may each be NULL.  workspace: asw_speckle_workspace_bytes
+ *     of device memory with arbitrary contents (the stage initialises what it reads); d, valid and
+ *     the outputs must not overlap it (ASW_E_INVALID).  The int32 at byte ASW_SPECKLE_STATUS_OFFSET
+ *     of the workspace is the status word: 0 after a run whose link-following loops all ended by
+ *     themselves, non-zero when one ran into its bound of width * height steps (the outputs are
+ *     then not to be trusted; it cannot happen unless the kernels are wrong).  All offsets 64-bit.
+ *   asw_lr_valid: valid[p] = 1 where the LR rule of asw_outputs.lr16 / asw_disp_mask passes
+ *     (p->lr_mode; code_ref / code_tar may be NULL with ASW_LR_NATIVE), else 0.
+ *   asw_speckle_mask16: out[p] = (uint16)d[p] where keep[p], else ASW_DISP16_INVALID;
+ *     ASW_E_INVALID for ndisp > 65535.
+ *   asw_speckle_mask_f32: out[p] = disp[p] where keep[p], else asw_disp_mask's quiet NaN
+ *     (0x7fc00000): asw_disp_fill fills it. */
+typedef struct asw_speckle_params {
+    int min_size;  /* 1..2^31-1: smallest component that is kept; default 32 */
+    int max_diff;  /* 0..65535: largest linked difference; default 1         */
+} asw_speckle_params;
+#define ASW_SPECKLE_STATUS_OFFSET 0
+void asw_speckle_params_default(asw_speckle_params *sp);
+int asw_speckle_params_check(const asw_params *p, const asw_speckle_params *sp);
+size_t asw_speckle_workspace_bytes(const asw_params *p);
+int asw_lr_valid(const asw_params *p, const int32_t *d_ref, const int32_t *d_tar, const uint8_t *code_ref,
+                 const uint8_t *code_tar, uint8_t *valid, void *stream);
+int asw_speckle(const asw_params *p, const asw_speckle_params *sp, const int32_t *d, const uint8_t *valid,
+                void *workspace, int32_t *label, int32_t *size, uint8_t *keep, void *stream);
+int asw_speckle_mask16(const asw_params *p, const int32_t *d, const uint8_t *keep, uint16_t *out, void *stream);
+int asw_speckle_mask_f32(const asw_params *p, const float *disp, const uint8_t *keep, float *out, void *stream);
 
 /* ---- d-sharded asw_WTA_REF (K/asw_wta_ref.cl:2-68): the refinement loop's volume
  * scan over a shard, the asw_wta_local protocol on the penalised values
@@ -725,6 +770,28 @@ int asw_set_census(asw_ctx *ctx, const asw_census_params *cp);
  * refinement penalty 0.085 * den * |val - d| was tuned against ASW-scale costs: the loops
  * run on the sums unchanged, their quality there is not claimed. */
 int asw_set_sgm(asw_ctx *ctx, const asw_sgm_params *sp);
+/* The speckle filter (asw_speckle) on the frame's pre-refinement d_ref: caller-owned host
+ * arrays, any may be NULL.  asw_set_speckle checks sp (asw_speckle_params_check), copies both
+ * structs and allocates the device maps and the workspace once; every later asw_match fills the
+ * registered arrays (asw_match_batch: pair b at offset b*H*W of each).  sp = NULL: off (the
+ * default; a frame then launches and allocates nothing new); o = NULL with sp set:
+ * ASW_E_INVALID, and so is filtered16 at ndisp > 65535.  valid is the LR rule (asw_lr_valid)
+ * on a context with lr_check, every pixel otherwise.  The kernels run on the first shard's
+ * stream after the consistency stage and the sub-pixel work, before the pre-refinement maps
+ * leave; with asw_set_graph on they run after the replay (not captured).  Their time is inside
+ * asw_timings.total and in no stage column.  disp_lr / disp_filled need the sub-pixel disp: the
+ * frame computes it once for asw_set_subpixel and for these outputs (a multi-shard context: the
+ * same one extra MIN all-reduce; with asw_create_rank every rank must switch alike).  The filter
+ * itself is per-pixel work on maps every rank holds: no new collective.  Works with census, SGM,
+ * both LR modes, any ndisp and any number of shards. */
+typedef struct asw_speckle_outputs {
+    uint16_t *filtered16;   /* [H][W] d_ref where valid and kept, else ASW_DISP16_INVALID            */
+    int32_t  *size;         /* [H][W] component size, 0 where invalid                                */
+    uint8_t  *keep;         /* [H][W]                                                                */
+    float    *disp_lr;      /* [H][W] sub-pixel disp where valid and kept, else NaN                  */
+    float    *disp_filled;  /* [H][W] asw_disp_fill of disp_lr                                       */
+} asw_speckle_outputs;
+int asw_set_speckle(asw_ctx *ctx, const asw_speckle_params *sp, const asw_speckle_outputs *o);
 
 #ifdef __cplusplus
 }

@@ -7,8 +7,9 @@ reference's kernel interface (:mod:`.kernels`), the one-GPU pipeline
 (:mod:`.pipeline`) and disparity-axis sharding over RCCL (:mod:`.distributed`).
 """
 from ._lib import (ASW_OK, COLOR_LAB, COLOR_RGB, DIR_H, DIR_V, LR_NATIVE, LR_U8, AswError,  # noqa: F401
-                   AswCensusParams, AswLibraryError, AswParams, AswSgmParams, AswSubpixelOutputs,
-                   default_census_params, default_params, default_sgm_params)
+                   AswCensusParams, AswLibraryError, AswParams, AswSgmParams, AswSpeckleParams,
+                   AswSubpixelOutputs, default_census_params, default_params, default_sgm_params,
+                   default_speckle_params)
 from .pipeline import (CrossMatcher, CrossResult, FrameContext, MatchResult, StereoMatcher,  # noqa: F401
                        comm_unique_id, make_params, match_frame, to_rgba)
 
@@ -16,5 +17,5 @@ __all__ = [
     "AswParams", "AswError", "AswLibraryError", "StereoMatcher", "MatchResult", "make_params", "match_frame",
     "FrameContext", "comm_unique_id", "CrossMatcher", "CrossResult",
     "to_rgba", "default_params", "AswSubpixelOutputs", "AswCensusParams", "default_census_params",
-    "AswSgmParams", "default_sgm_params",
+    "AswSgmParams", "default_sgm_params", "AswSpeckleParams", "default_speckle_params",
 ]

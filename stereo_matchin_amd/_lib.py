@@ -144,6 +144,26 @@ class AswSgmParams(ctypes.Structure):
         return AswSgmParams(self.paths, self.p1, self.p2)
 
 
+class AswSpeckleParams(ctypes.Structure):
+    """Mirror of ``asw_speckle_params`` (include/asw.h): the smallest component that is kept
+    and the largest linked difference of the speckle filter."""
+
+    _fields_ = [("min_size", ctypes.c_int), ("max_diff", ctypes.c_int)]
+
+    def copy(self) -> "AswSpeckleParams":
+        return AswSpeckleParams(self.min_size, self.max_diff)
+
+
+class AswSpeckleOutputs(ctypes.Structure):
+    """Mirror of ``asw_speckle_outputs``: caller-owned host [H][W] arrays, any may be NULL."""
+
+    _fields_ = [("filtered16", ctypes.c_void_p), ("size", ctypes.c_void_p), ("keep", ctypes.c_void_p),
+                ("disp_lr", ctypes.c_void_p), ("disp_filled", ctypes.c_void_p)]
+
+
+SPECKLE_STATUS_OFFSET = 0  # ASW_SPECKLE_STATUS_OFFSET: the int32 status word of asw_speckle's workspace
+
+
 class AswCrossTimings(ctypes.Structure):
     """Mirror of ``asw_cross_timings``: the reference's columns (main.cpp:394-410), ms."""
 
@@ -180,6 +200,7 @@ RP = ctypes.POINTER(AswRefineParams)
 CP = ctypes.POINTER(AswCrossParams)
 NP = ctypes.POINTER(AswCensusParams)
 SP = ctypes.POINTER(AswSgmParams)
+KP = ctypes.POINTER(AswSpeckleParams)
 I = ctypes.c_int
 
 # name -> (restype, argtypes).  Every function declared in include/asw.h.
@@ -268,6 +289,14 @@ SIGNATURES = {
     "asw_sgm_path": (I, [PP, SP, I, P, P, I, P]),
     "asw_sgm": (I, [PP, SP, P, P, P, P]),
     "asw_set_sgm": (I, [P, SP]),
+    "asw_speckle_params_default": (None, [KP]),
+    "asw_speckle_params_check": (I, [PP, KP]),
+    "asw_speckle_workspace_bytes": (ctypes.c_size_t, [PP]),
+    "asw_lr_valid": (I, [PP, P, P, P, P, P, P]),
+    "asw_speckle": (I, [PP, KP, P, P, P, P, P, P, P]),
+    "asw_speckle_mask16": (I, [PP, P, P, P, P]),
+    "asw_speckle_mask_f32": (I, [PP, P, P, P, P]),
+    "asw_set_speckle": (I, [P, KP, ctypes.POINTER(AswSpeckleOutputs)]),
     "asw_tune_set": (I, [I, I]),
     "asw_pass_kernel": (I, [I, I, ctypes.c_char_p, I]),
     "asw_device_name": (I, [I, ctypes.c_char_p, I]),
@@ -416,6 +445,25 @@ def sgm_params_of(sgm) -> AswSgmParams | None:
     if sgm is None or sgm is False:
         return None
     return default_sgm_params() if sgm is True else sgm.copy()
+
+
+def default_speckle_params(**kw) -> AswSpeckleParams:
+    """The default speckle filter (min_size 32, max_diff 1), overridable."""
+    sp = AswSpeckleParams()
+    _load().asw_speckle_params_default(ctypes.byref(sp))
+    for k, v in kw.items():
+        if not hasattr(sp, k):
+            raise TypeError(f"unknown asw_speckle_params field {k!r}")
+        setattr(sp, k, v)
+    return sp
+
+
+def speckle_params_of(speckle) -> AswSpeckleParams | None:
+    """The ``speckle=`` keyword of the matchers: None / False (off), True (the defaults) or an
+    AswSpeckleParams."""
+    if speckle is None or speckle is False:
+        return None
+    return default_speckle_params() if speckle is True else speckle.copy()
 
 
 def disp_pitch(p: AswParams) -> int:

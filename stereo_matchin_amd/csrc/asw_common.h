@@ -29,6 +29,21 @@ __host__ __device__ inline int code_u8(int d, int D) {
     return c > 255 ? 255 : (c < 0 ? 0 : (int)c);
 }
 
+// The left-right rule of asw_outputs.lr16, asw_disp_mask and asw_lr_valid at pixel p, written
+// once: ASW_LR_U8 compares the 8-bit codes like K/consist.cl:20-30, ASW_LR_NATIVE the indices
+// (|d_ref - d_tar| <= 1).  dr = d_ref[p]; the code pointers are read with ASW_LR_U8 only.
+__device__ __forceinline__ bool lr_consistent(int mode, int D, long long p, int dr, const int32_t *d_tar,
+                                              const uint8_t *code_ref, const uint8_t *code_tar) {
+    if (mode == ASW_LR_U8) {
+        const float scale = (float)(D - 1);
+        const float qr = ((float)code_ref[p] / 255.0f) * scale;
+        const float qt = ((float)code_tar[p] / 255.0f) * scale;
+        return fabsf(qt - qr) < 1.001f;
+    }
+    const int dd = dr - d_tar[p];
+    return dd <= 1 && dd >= -1;
+}
+
 void set_hip_error(hipError_t e);
 
 // last plane + 1 of the context's disparity shard (asw_params.d_end < 0: ndisp)

@@ -108,6 +108,16 @@ struct asw_ctx {
     asw_sgm_params sgm{};
     bool sgm_on = false;
     void *sgm_ws = nullptr;
+    // asw_set_speckle: the speckle filter on the pre-refinement d_ref: parameters, the registered
+    // host arrays, the validity map (lr_check), workspace and device maps (shard 0's device)
+    asw_speckle_params spk{};
+    asw_speckle_outputs spo{};
+    bool spk_on = false;
+    uint8_t *spk_valid = nullptr, *spk_keep = nullptr;
+    void *spk_ws = nullptr;
+    int32_t *spk_size = nullptr;
+    uint16_t *spk_f16 = nullptr;
+    float *spk_lr = nullptr, *spk_fill = nullptr;
 };
 
 namespace {
@@ -167,16 +177,7 @@ __global__ void k_disp16(long long n, int D, int mode, int lr, const int32_t *d_
     const int dr = d_ref[p];
     if (disp16) disp16[p] = (uint16_t)dr;
     if (!lr16 || !lr) return;
-    bool cons;
-    if (mode == ASW_LR_U8) {
-        const float scale = (float)(D - 1);
-        const float qr = ((float)code_ref[p] / 255.0f) * scale;
-        const float qt = ((float)code_tar[p] / 255.0f) * scale;
-        cons = fabsf(qt - qr) < 1.001f;
-    } else {
-        const int dd = dr - d_tar[p];
-        cons = dd <= 1 && dd >= -1;
-    }
+    const bool cons = asw::lr_consistent(mode, D, p, dr, d_tar, code_ref, code_tar);
     lr16[p] = cons ? (uint16_t)dr : (uint16_t)ASW_DISP16_INVALID;
 }
 
@@ -339,7 +340,8 @@ int destroy_ctx(asw_ctx *c) {
                     c->lr_red, c->disp, c->disp16, c->lr16, c->rws, c->est, c->post_red, c->final_rgba,
                     c->nrws, c->n_est, c->n_dt, c->n_dr, c->n_post16, c->n_final16,
                     c->sgm_ws, c->sp_disp, c->sp_lr, c->sp_fill, c->cr_med_l, c->cr_med_r, c->cr_init, c->cr_final,
-                    c->cr_arms_l, c->cr_arms_r, c->cr_d0, c->cr_code0, c->cr_code1};
+                    c->cr_arms_l, c->cr_arms_r, c->cr_d0, c->cr_code0, c->cr_code1,
+                    c->spk_valid, c->spk_keep, c->spk_ws, c->spk_size, c->spk_f16, c->spk_lr, c->spk_fill};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (hipEvent_t e : c->ev)
@@ -743,6 +745,27 @@ int subpixel_work(asw_ctx *c) {
     return ASW_OK;
 }
 
+// whether the registered speckle outputs need the sub-pixel disp map (subpixel_work)
+bool speckle_wants_disp(const asw_ctx *c) { return c->spk_on && (c->spo.disp_lr || c->spo.disp_filled); }
+
+// The speckle filter (asw_set_speckle) on the frame's d_ref, on shard 0's stream after the
+// consistency stage and the sub-pixel work: the LR rule as the validity map (lr_check), the
+// components, then the masked maps that were asked for.
+int speckle_work(asw_ctx *c) {
+    const asw_params *p = &c->p;
+    hipStream_t st = c->sh[0].stream;
+    const uint8_t *valid = nullptr;
+    if (p->lr_check) {
+        ASWCHK(asw_lr_valid(p, c->d_ref, c->d_tar, c->code_ref, c->code_tar, c->spk_valid, st));
+        valid = c->spk_valid;
+    }
+    ASWCHK(asw_speckle(p, &c->spk, c->d_ref, valid, c->spk_ws, nullptr, c->spk_size, c->spk_keep, st));
+    if (c->spo.filtered16) ASWCHK(asw_speckle_mask16(p, c->d_ref, c->spk_keep, c->spk_f16, st));
+    if (speckle_wants_disp(c)) ASWCHK(asw_speckle_mask_f32(p, c->sp_disp, c->spk_keep, c->spk_lr, st));
+    if (c->spo.disp_filled) ASWCHK(asw_disp_fill(p, c->spk_lr, c->spk_fill, st));
+    return ASW_OK;
+}
+
 // The cross-based matcher of a frame (asw_set_cross; main.cpp:272-354), on shard 0's
 // stream ahead of the ASW stages: it uploads the pair itself and borrows the shard's two
 // cost volumes, which the ASW stages overwrite afterwards.  The registered host arrays
@@ -848,7 +871,8 @@ int match_one(asw_ctx *c, const uint8_t *left_rgba, const uint8_t *right_rgba, a
     std::vector<hipEvent_t> &ev = c->ev;
     // event slots: 0 h2d start, 1 h2d end = raw start, 2 raw end, 3.. 3+2r pass marks,
     // then exchange end, wta end, consistency end (= end of `total`), pre-refinement d2h end,
-    // refine end, d2h end; sub-pixel maps on: their start (they end at "consistency end")
+    // refine end, d2h end; sub-pixel maps or speckle filter on: their start (they end at
+    // "consistency end")
     const int e_pass0 = 3, e_x = e_pass0 + 2 * r + 1, e_wta = e_x + 1, e_cons = e_x + 2, e_pre = e_x + 3,
               e_ref = e_x + 4, e_d2h = e_x + 5, e_sub = e_x + 6;
     const bool graphed = c->graph && c->comm == COMM_NONE;
@@ -888,12 +912,24 @@ int match_one(asw_ctx *c, const uint8_t *left_rgba, const uint8_t *right_rgba, a
             HIPCHK(hipGetLastError());
         }
     }
-    if (c->sub_on) {  // never captured: launched on the stream after the graph replay
-        HIPCHK(hipEventRecord(ev[e_sub], st));
-        ASWCHK(subpixel_work(c));
-    }
+    // the sub-pixel maps and the speckle filter: never captured, launched on the stream after
+    // the graph replay; the disp map is computed once for both
+    const bool sub_work = c->sub_on || speckle_wants_disp(c), post_work = sub_work || c->spk_on;
+    if (post_work) HIPCHK(hipEventRecord(ev[e_sub], st));
+    if (sub_work) ASWCHK(subpixel_work(c));
+    if (c->spk_on) ASWCHK(speckle_work(c));
     HIPCHK(hipEventRecord(ev[e_cons], st));
     // pre-refinement outputs leave before the loop updates its buffers in place
+    if (c->spk_on) {
+        const asw_speckle_outputs &so = c->spo;
+        const size_t off = pair * S;
+        if (so.filtered16) HIPCHK(hipMemcpyAsync(so.filtered16 + off, c->spk_f16, S * 2, hipMemcpyDeviceToHost, st));
+        if (so.size) HIPCHK(hipMemcpyAsync(so.size + off, c->spk_size, S * 4, hipMemcpyDeviceToHost, st));
+        if (so.keep) HIPCHK(hipMemcpyAsync(so.keep + off, c->spk_keep, S, hipMemcpyDeviceToHost, st));
+        if (so.disp_lr) HIPCHK(hipMemcpyAsync(so.disp_lr + off, c->spk_lr, S * 4, hipMemcpyDeviceToHost, st));
+        if (so.disp_filled)
+            HIPCHK(hipMemcpyAsync(so.disp_filled + off, c->spk_fill, S * 4, hipMemcpyDeviceToHost, st));
+    }
     if (c->sub_on) {
         const size_t off = pair * S;
         if (c->sub.disp) HIPCHK(hipMemcpyAsync(c->sub.disp + off, c->sp_disp, S * 4, hipMemcpyDeviceToHost, st));
@@ -985,7 +1021,8 @@ int match_one(asw_ctx *c, const uint8_t *left_rgba, const uint8_t *right_rgba, a
         // an exchange with no peer, is inside aggregation_total and both columns are 0)
         t->exchange = sharded && !c->sgm_on ? ms_between(ev[e_pass0 + 2 * r], ev[e_x]) : 0.0;
         t->wta = sharded ? t->exchange : ms_between(ev[e_x], ev[e_wta]);
-        t->consistency = ms_between(ev[e_wta], ev[c->sub_on ? e_sub : e_cons]);  // the sub-pixel maps: in no column
+        // the sub-pixel maps and the speckle filter: in no column
+        t->consistency = ms_between(ev[e_wta], ev[post_work ? e_sub : e_cons]);
         t->total = ms_between(ev[1], ev[e_cons]);
         t->refine = refine || nrefine ? ms_between(ev[e_pre], ev[e_ref]) : 0.0;
         t->d2h = ms_between(ev[e_cons], ev[e_pre]) + ms_between(ev[e_ref], ev[e_d2h]);
@@ -1138,14 +1175,9 @@ int asw_set_refine(asw_ctx *c, const asw_refine_params *rp) {
     return ASW_OK;
 }
 
-int asw_set_subpixel(asw_ctx *c, const asw_subpixel_outputs *o) {
-    if (!c) return ASW_E_INVALID;
-    if (!o || (!o->disp && !o->disp_lr && !o->disp_filled)) {
-        c->sub_on = false;
-        c->sub = asw_subpixel_outputs{};
-        return ASW_OK;
-    }
-    if ((o->disp_lr || o->disp_filled) && !c->p.lr_check) return ASW_E_INVALID;  // they are LR-masked maps
+// the device disp map of subpixel_work (asw_set_subpixel, asw_set_speckle's float outputs) and,
+// on a sharded frame, the operands of its one all-reduce; allocated once
+static int alloc_subpixel_disp(asw_ctx *c) {
     const size_t S = frame_pixels(&c->p);
     if (c->comm != COMM_NONE) {
         for (int i = 0; i < c->n; ++i) {
@@ -1161,10 +1193,50 @@ int asw_set_subpixel(asw_ctx *c, const asw_subpixel_outputs *o) {
         ASWCHK(dev_alloc(&c->red_tmp, (size_t)(c->n - 1) * S * 12));
     }
     if (!c->sp_disp) ASWCHK(dev_alloc(&c->sp_disp, S * 4));
+    return ASW_OK;
+}
+
+int asw_set_subpixel(asw_ctx *c, const asw_subpixel_outputs *o) {
+    if (!c) return ASW_E_INVALID;
+    if (!o || (!o->disp && !o->disp_lr && !o->disp_filled)) {
+        c->sub_on = false;
+        c->sub = asw_subpixel_outputs{};
+        return ASW_OK;
+    }
+    if ((o->disp_lr || o->disp_filled) && !c->p.lr_check) return ASW_E_INVALID;  // they are LR-masked maps
+    const size_t S = frame_pixels(&c->p);
+    ASWCHK(alloc_subpixel_disp(c));
     if ((o->disp_lr || o->disp_filled) && !c->sp_lr) ASWCHK(dev_alloc(&c->sp_lr, S * 4));
     if (o->disp_filled && !c->sp_fill) ASWCHK(dev_alloc(&c->sp_fill, S * 4));
     c->sub = *o;
     c->sub_on = true;
+    return ASW_OK;
+}
+
+int asw_set_speckle(asw_ctx *c, const asw_speckle_params *sp, const asw_speckle_outputs *o) {
+    if (!c) return ASW_E_INVALID;
+    if (!sp) {
+        c->spk_on = false;
+        c->spo = asw_speckle_outputs{};
+        return ASW_OK;
+    }
+    if (!o) return ASW_E_INVALID;
+    ASWCHK(asw_speckle_params_check(&c->p, sp));
+    if (o->filtered16 && c->p.ndisp > 65535) return ASW_E_INVALID;  // asw_speckle_mask16's rule
+    const size_t S = frame_pixels(&c->p);
+    const bool want_disp = o->disp_lr || o->disp_filled;
+    if (want_disp) ASWCHK(alloc_subpixel_disp(c));
+    HIPCHK(hipSetDevice(c->sh[0].device));
+    if (c->p.lr_check && !c->spk_valid) ASWCHK(dev_alloc(&c->spk_valid, S));
+    if (!c->spk_ws) ASWCHK(dev_alloc(&c->spk_ws, asw_speckle_workspace_bytes(&c->p)));
+    if (!c->spk_size) ASWCHK(dev_alloc(&c->spk_size, S * 4));
+    if (!c->spk_keep) ASWCHK(dev_alloc(&c->spk_keep, S));
+    if (o->filtered16 && !c->spk_f16) ASWCHK(dev_alloc(&c->spk_f16, S * 2));
+    if (want_disp && !c->spk_lr) ASWCHK(dev_alloc(&c->spk_lr, S * 4));
+    if (o->disp_filled && !c->spk_fill) ASWCHK(dev_alloc(&c->spk_fill, S * 4));
+    c->spk = *sp;
+    c->spo = *o;
+    c->spk_on = true;
     return ASW_OK;
 }
 

@@ -84,16 +84,7 @@ __global__ __launch_bounds__(256) void k_disp_mask(long long n, int D, int mode,
                                                    float *__restrict__ disp_lr) {
     const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
-    bool cons;
-    if (mode == ASW_LR_U8) {
-        const float scale = (float)(D - 1);
-        const float qr = ((float)code_ref[p] / 255.0f) * scale;
-        const float qt = ((float)code_tar[p] / 255.0f) * scale;
-        cons = fabsf(qt - qr) < 1.001f;
-    } else {
-        const int dd = d_ref[p] - d_tar[p];
-        cons = dd <= 1 && dd >= -1;
-    }
+    const bool cons = lr_consistent(mode, D, p, d_ref[p], d_tar, code_ref, code_tar);
     disp_lr[p] = cons ? disp[p] : quiet_nan();
 }
 

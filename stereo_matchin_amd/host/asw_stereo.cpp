@@ -46,7 +46,12 @@
 //   * --sgm aggregates by semi-global matching (asw_set_sgm; --sgm-paths 4|8,
 //     --sgm-penalties P1,P2) in place of the supports and the ASW passes: --taps and --iters
 //     are then not read.  The outputs and the TSV columns are unchanged; `total aggregation`
-//     then holds the SGM launches, supp_w and the two pass means are 0.
+//     then holds the SGM launches, supp_w and the two pass means are 0;
+//   * --speckle runs the speckle filter (asw_set_speckle; --speckle-size N, --speckle-diff N)
+//     on the pre-refinement left map and writes asw_speckle16.png (16-bit grey, the disparity
+//     index, 65535 where the component is smaller than N pixels or the LR check fails); with
+//     --subpixel also asw_disparity_sub_speckle.pfm and asw_disparity_sub_speckle16.png, the
+//     --subpixel files under the filter's mask.  Every other file and the TSV are unchanged.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -76,6 +81,9 @@ struct Options {
     bool sgm = false;  // --sgm: semi-global matching in place of the ASW passes (asw_set_sgm)
     bool sgm_paths_given = false, sgm_penalties_given = false;  // any integer reaches asw_set_sgm
     int sgm_paths = 0, sgm_p1 = 0, sgm_p2 = 0;
+    bool speckle = false;  // --speckle: the speckle filter on the left map (asw_set_speckle)
+    bool speckle_size_given = false, speckle_diff_given = false;  // any integer reaches asw_set_speckle
+    int speckle_size = 0, speckle_diff = 0;
 };
 
 void usage() {
@@ -86,6 +94,11 @@ void usage() {
                  "                  [--subpixel] [--cross [--cross-arm N] [--cross-tau N]]\n"
                  "                  [--census [--census-win WxH] [--census-weights A,C]]\n"
                  "                  [--sgm [--sgm-paths 4|8] [--sgm-penalties P1,P2]]\n"
+                 "                  [--speckle [--speckle-size N] [--speckle-diff N]]\n"
+                 "  --speckle   speckle filter on the left map: components of 4-neighbours that differ by at most\n"
+                 "              --speckle-diff (default 1) and hold fewer than --speckle-size pixels (default 32) are\n"
+                 "              removed: asw_speckle16.png (16-bit index, 65535 = removed or inconsistent; --ndisp <= 65535);\n"
+                 "              with --subpixel also asw_disparity_sub_speckle.pfm and asw_disparity_sub_speckle16.png\n"
                  "  --refine K  refinement iterations + 3x3 median (default 6, 0 = off): asw_disparity.png and\n"
                  "              asw_consistency_post-reff.png; with --ndisp > 256 or --native-lr the loop runs on disparity\n"
                  "              indices and writes asw_disparity16.png and asw_consistency_post16.png (65535 = inconsistent)\n"
@@ -163,6 +176,19 @@ bool parse(int argc, char **argv, Options &o) {
             char tail = 0;
             if (std::sscanf(v, "%d,%d%c", &o.sgm_p1, &o.sgm_p2, &tail) != 2) return false;
             o.sgm = o.sgm_penalties_given = true;
+        }
+        else if (a == "--speckle") o.speckle = true;
+        else if (a == "--speckle-size") {
+            if (!(v = next("--speckle-size"))) return false;
+            char tail = 0;
+            if (std::sscanf(v, "%d%c", &o.speckle_size, &tail) != 1) return false;
+            o.speckle = o.speckle_size_given = true;
+        }
+        else if (a == "--speckle-diff") {
+            if (!(v = next("--speckle-diff"))) return false;
+            char tail = 0;
+            if (std::sscanf(v, "%d%c", &o.speckle_diff, &tail) != 1) return false;
+            o.speckle = o.speckle_diff_given = true;
         }
         else if (a == "--lab") o.lab = true;
         else if (a == "--no-lr") o.lr = false;
@@ -352,6 +378,28 @@ int main(int argc, char **argv) {
                 continue;
             }
         }
+        // speckle filter: registered once, run after the consistency stage by every asw_match
+        const bool spk_sub = o.speckle && o.subpixel;
+        std::vector<uint16_t> spk16(o.speckle ? S : 0);
+        std::vector<float> spk_lr(spk_sub ? S : 0), spk_fill(spk_sub ? S : 0);
+        if (o.speckle) {
+            asw_speckle_params kp;
+            asw_speckle_params_default(&kp);
+            if (o.speckle_size_given) kp.min_size = o.speckle_size;
+            if (o.speckle_diff_given) kp.max_diff = o.speckle_diff;
+            asw_speckle_outputs ko;
+            std::memset(&ko, 0, sizeof ko);
+            ko.filtered16 = spk16.data();
+            ko.disp_lr = spk_sub ? spk_lr.data() : nullptr;
+            ko.disp_filled = spk_sub ? spk_fill.data() : nullptr;
+            st = asw_set_speckle(ctx, &kp, &ko);
+            if (st != ASW_OK) {
+                std::fprintf(stderr, "%s: asw_set_speckle: %s\n", folder.c_str(), asw_strerror(st));
+                ++failures;
+                asw_destroy(ctx);
+                continue;
+            }
+        }
         // cross-based matcher: registered once, run ahead of the ASW stages by every asw_match
         std::vector<uint8_t> cr_init(o.cross ? S * 4 : 0), cr_fin(o.cross ? S * 4 : 0), cr_med(o.cross ? S * 4 : 0);
         asw_cross_timings ct;
@@ -476,6 +524,22 @@ int main(int argc, char **argv) {
             for (size_t i = 0; i < S; ++i) q[i] = (uint16_t)std::nearbyintf(dense[i] * 64.0f);
             e = asw_host::pfm_save(dir + "/asw_disparity_sub.pfm", pf.data(), L.width, L.height);
             if (e.empty()) e = asw_host::png_save16(dir + "/asw_disparity_sub16.png", q.data(), L.width, L.height);
+            if (!e.empty()) {
+                std::fprintf(stderr, "%s: %s\n", folder.c_str(), e.c_str());
+                ++failures;
+            }
+        }
+        if (o.speckle) {
+            e = asw_host::png_save16(dir + "/asw_speckle16.png", spk16.data(), L.width, L.height);
+            if (e.empty() && spk_sub) {  // the encodings of the --subpixel files
+                for (float &v : spk_lr)
+                    if (v != v) v = INFINITY;
+                std::vector<uint16_t> q(S);
+                for (size_t i = 0; i < S; ++i) q[i] = (uint16_t)std::nearbyintf(spk_fill[i] * 64.0f);
+                e = asw_host::pfm_save(dir + "/asw_disparity_sub_speckle.pfm", spk_lr.data(), L.width, L.height);
+                if (e.empty())
+                    e = asw_host::png_save16(dir + "/asw_disparity_sub_speckle16.png", q.data(), L.width, L.height);
+            }
             if (!e.empty()) {
                 std::fprintf(stderr, "%s: %s\n", folder.c_str(), e.c_str());
                 ++failures;

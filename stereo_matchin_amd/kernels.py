@@ -457,6 +457,73 @@ def disp_fill(p: AswParams, disp_lr: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ------------------------------------------------------------------ speckle filter
+# No reference counterpart: connected components of similar disparity (include/asw.h §speckle).
+
+def lr_valid(p: AswParams, d_ref, d_tar, code_ref=None, code_tar=None) -> torch.Tensor:
+    """asw_lr_valid: uint8 [H][W], 1 where the LR check passes (p.lr_mode), 0 elsewhere."""
+    _expect(d_ref, (p.height, p.width), torch.int32, "d_ref")
+    _expect(d_tar, (p.height, p.width), torch.int32, "d_tar")
+    out = torch.empty((p.height, p.width), dtype=torch.uint8, device=d_ref.device)
+    _lib.check(_lib.lib().asw_lr_valid(ctypes.byref(p), _ptr(d_ref), _ptr(d_tar), _ptr(code_ref), _ptr(code_tar),
+                                       _ptr(out), _stream(d_ref.device)), "asw_lr_valid")
+    return out
+
+
+def speckle_workspace(p: AswParams, device) -> torch.Tensor:
+    """asw_speckle_workspace_bytes of device memory (uint8), contents arbitrary."""
+    return torch.empty(int(_lib.lib().asw_speckle_workspace_bytes(ctypes.byref(p))), dtype=torch.uint8, device=device)
+
+
+def speckle_status(workspace: torch.Tensor) -> int:
+    """The status word asw_speckle left in its workspace: 0 unless a link-following loop ran
+    into its bound (synchronises)."""
+    o = _lib.SPECKLE_STATUS_OFFSET
+    return int(workspace[o:o + 4].view(torch.int32).item())
+
+
+def speckle(p: AswParams, sp, d: torch.Tensor, valid: torch.Tensor | None = None,
+            workspace: torch.Tensor | None = None, want=("label", "size", "keep"), return_status: bool = False):
+    """asw_speckle: ``(label int32, size int32, keep uint8)`` [H][W] of the connected
+    components of ``d`` (int32) under ``valid`` (uint8, None = every pixel); an output not
+    named in ``want`` is not computed and returned as None.  ``return_status``: also the
+    workspace's status word (0 = every loop ended by itself), as a fourth element."""
+    H, W = p.height, p.width
+    _expect(d, (H, W), torch.int32, "d")
+    if valid is not None:
+        _expect(valid, (H, W), torch.uint8, "valid")
+    if workspace is None:
+        workspace = speckle_workspace(p, d.device)
+    label = torch.empty((H, W), dtype=torch.int32, device=d.device) if "label" in want else None
+    size = torch.empty((H, W), dtype=torch.int32, device=d.device) if "size" in want else None
+    keep = torch.empty((H, W), dtype=torch.uint8, device=d.device) if "keep" in want else None
+    _lib.check(_lib.lib().asw_speckle(ctypes.byref(p), ctypes.byref(sp), _ptr(d), _ptr(valid), _ptr(workspace),
+                                      _ptr(label), _ptr(size), _ptr(keep), _stream(d.device)), "asw_speckle")
+    if return_status:
+        return label, size, keep, speckle_status(workspace)
+    return label, size, keep
+
+
+def speckle_mask16(p: AswParams, d: torch.Tensor, keep: torch.Tensor) -> torch.Tensor:
+    """asw_speckle_mask16: d where keep, else 0xFFFF; a uint16 map in int16 storage."""
+    _expect(d, (p.height, p.width), torch.int32, "d")
+    _expect(keep, (p.height, p.width), torch.uint8, "keep")
+    out = torch.empty((p.height, p.width), dtype=torch.int16, device=d.device)
+    _lib.check(_lib.lib().asw_speckle_mask16(ctypes.byref(p), _ptr(d), _ptr(keep), _ptr(out), _stream(d.device)),
+               "asw_speckle_mask16")
+    return out
+
+
+def speckle_mask_f32(p: AswParams, disp: torch.Tensor, keep: torch.Tensor) -> torch.Tensor:
+    """asw_speckle_mask_f32: disp where keep, NaN elsewhere (what disp_fill fills)."""
+    _expect(disp, (p.height, p.width), torch.float32, "disp")
+    _expect(keep, (p.height, p.width), torch.uint8, "keep")
+    out = torch.empty_like(disp)
+    _lib.check(_lib.lib().asw_speckle_mask_f32(ctypes.byref(p), _ptr(disp), _ptr(keep), _ptr(out),
+                                               _stream(disp.device)), "asw_speckle_mask_f32")
+    return out
+
+
 # ------------------------------------------------------------------ cross-based matcher
 # main.cpp:243-411: Median, Cross, Aggregation, Integral_h, Oii_hcross, Integral_v,
 # Oii_vcross, Init_disparity, Disparity.  Arm maps are int8 [H][W][4] = (h-, h+, v-, v+).

@@ -43,6 +43,10 @@ class MatchResult:
     disp: torch.Tensor | None = None         # d_ref + parabola offset of the neighbouring planes
     disp_lr: torch.Tensor | None = None      # disp where the LR check passes, NaN elsewhere
     disp_filled: torch.Tensor | None = None  # disp_lr with its holes filled per row
+    # speckle filter (StereoMatcher(speckle=...)): connected components of d_ref under the LR rule
+    speckle_keep: torch.Tensor | None = None  # uint8 [H][W]: valid and in a component of >= min_size pixels
+    speckle_size: torch.Tensor | None = None  # int32 [H][W] component size, 0 where invalid
+    filtered16: torch.Tensor | None = None    # uint16 in int16 storage: d_ref where kept, else 0xFFFF
 
 
 class StereoMatcher:
@@ -59,9 +63,14 @@ class StereoMatcher:
     ``sgm``: None (the ASW passes), True (8 paths, P1 16, P2 128) or an AswSgmParams:
     semi-global matching (asw_sgm) on the uint16 raw cost in place of the supports and the
     passes; ``taps`` and ``iters`` are then not read and no support array is allocated
-    (include/asw.h §SGM)."""
+    (include/asw.h §SGM).
 
-    def __init__(self, params: AswParams, device="cuda", den_cache: bool = True, census=None, sgm=None):
+    ``speckle``: None (off), True (min_size 32, max_diff 1) or an AswSpeckleParams: ``match``
+    then runs the speckle filter (asw_speckle) on d_ref, valid where the LR check passes (every
+    pixel without it), and fills ``speckle_keep`` / ``speckle_size`` / ``filtered16``."""
+
+    def __init__(self, params: AswParams, device="cuda", den_cache: bool = True, census=None, sgm=None,
+                 speckle=None):
         st = _lib.params_check(params)
         if st != _lib.ASW_OK:
             raise _lib.AswError(st, "asw_params_check")
@@ -71,6 +80,10 @@ class StereoMatcher:
             _lib.check(_lib.lib().asw_census_params_check(ctypes.byref(self.p), ctypes.byref(self.census)),
                        "asw_census_params_check")
         self.sgm = _lib.sgm_params_of(sgm)
+        self.speckle = _lib.speckle_params_of(speckle)
+        if self.speckle is not None:
+            _lib.check(_lib.lib().asw_speckle_params_check(ctypes.byref(self.p), ctypes.byref(self.speckle)),
+                       "asw_speckle_params_check")
         self.device = torch.device(device)
         dev = self.device
         self.local = None
@@ -201,6 +214,11 @@ class StereoMatcher:
             res.disp = K.subpixel(p, cost, d_ref)
             if lr is not None:
                 res.disp_lr, res.disp_filled = subpixel_lr_maps(p, res)
+        if self.speckle is not None:
+            valid = K.lr_valid(p, d_ref, d_tar, code_ref, code_tar) if lr is not None else None
+            _, res.speckle_size, res.speckle_keep = K.speckle(p, self.speckle, d_ref, valid, want=("size", "keep"))
+            if p.ndisp <= 65535:
+                res.filtered16 = K.speckle_mask16(p, d_ref, res.speckle_keep)
         return res
 
     def refine(self, res: MatchResult, left: torch.Tensor, right: torch.Tensor, rp=None) -> dict:
@@ -303,7 +321,8 @@ class FrameContext:
     """
 
     def __init__(self, params: AswParams, devices=(0,), rank: int | None = None, nranks: int | None = None,
-                 comm_id: bytes | None = None, refine=None, graph: bool = False, census=None, sgm=None):
+                 comm_id: bytes | None = None, refine=None, graph: bool = False, census=None, sgm=None,
+                 speckle=None):
         self.L = _lib.lib()
         self.p = params.copy()
         self.ctx = ctypes.c_void_p()
@@ -343,6 +362,36 @@ class FrameContext:
         self.sgm = None
         if sgm is not None and sgm is not False:
             self.set_sgm(sgm)
+        self.speckle = None
+        if speckle is not None and speckle is not False:
+            self.set_speckle(speckle)
+
+    def set_speckle(self, speckle=True) -> None:
+        """``asw_set_speckle``: the speckle filter (asw_speckle) on the pre-refinement d_ref of
+        every later match, valid where the LR check passes (every pixel on a context without
+        it).  Its results arrive under ``speckle_filtered16`` (ndisp <= 65535), ``speckle_size``
+        and ``speckle_keep``, and with ``subpixel=True`` on a context with the LR check also
+        ``speckle_disp_lr`` (NaN holes) and ``speckle_disp_filled``.  ``speckle``: an
+        AswSpeckleParams, True for the defaults (min_size 32, max_diff 1), None / False to turn
+        it off again."""
+        sp = _lib.speckle_params_of(speckle)
+        if sp is None:
+            _lib.check(self.L.asw_set_speckle(self.ctx, None, None), "asw_set_speckle")
+        else:  # validated here with empty outputs; match_batch registers each call's arrays
+            _lib.check(self.L.asw_set_speckle(self.ctx, ctypes.byref(sp), ctypes.byref(_lib.AswSpeckleOutputs())),
+                       "asw_set_speckle")
+        self.speckle = sp
+
+    def _speckle_outputs(self, B: int, subpixel: bool):
+        H, W = self.p.height, self.p.width
+        spk = {"speckle_size": np.empty((B, H, W), np.int32), "speckle_keep": np.empty((B, H, W), np.uint8)}
+        if self.p.ndisp <= 65535:
+            spk["speckle_filtered16"] = np.empty((B, H, W), np.uint16)
+        if subpixel and self.p.lr_check:
+            spk["speckle_disp_lr"] = np.empty((B, H, W), np.float32)
+            spk["speckle_disp_filled"] = np.empty((B, H, W), np.float32)
+        ko = _lib.AswSpeckleOutputs(**{k[len("speckle_"):]: v.ctypes.data for k, v in spk.items()})
+        return spk, ko
 
     def set_sgm(self, sgm=True) -> None:
         """``asw_set_sgm``: semi-global matching (asw_sgm) on the uint16 raw cost in place of
@@ -452,6 +501,11 @@ class FrameContext:
             no = _lib.AswRefineNativeOutputs(*[v.ctypes.data for v in nat.values()])
             _lib.check(self.L.asw_set_refine_native(self.ctx, ctypes.byref(self.refine_native), ctypes.byref(no)),
                        "asw_set_refine_native")
+        spk = {}
+        if self.speckle is not None and B:
+            spk, ko = self._speckle_outputs(B, subpixel)
+            _lib.check(self.L.asw_set_speckle(self.ctx, ctypes.byref(self.speckle), ctypes.byref(ko)),
+                       "asw_set_speckle")
         try:
             _lib.check(self.L.asw_match_batch(self.ctx, lefts.ctypes.data, rights.ctypes.data, B, oarr, tarr),
                        "asw_match_batch")
@@ -463,7 +517,9 @@ class FrameContext:
                                              ctypes.byref(_lib.AswRefineNativeOutputs()))
             if cr:  # this call's arrays leave the context; the matcher stays on
                 self.L.asw_set_cross(self.ctx, ctypes.byref(self.cross[0]), ctypes.byref(_lib.AswCrossOutputs()))
-        for k, v in {**sub, **cr, **nat}.items():
+            if spk:  # this call's arrays leave the context; the filter stays on
+                self.L.asw_set_speckle(self.ctx, ctypes.byref(self.speckle), ctypes.byref(_lib.AswSpeckleOutputs()))
+        for k, v in {**sub, **cr, **nat, **spk}.items():
             for b in range(B):
                 outs[b][k] = v[b]
         if ctim is not None:
@@ -501,8 +557,8 @@ def comm_unique_id() -> bytes:
 
 def match_frame(params: AswParams, left_rgba: np.ndarray, right_rgba: np.ndarray, device: int = 0,
                 want_cost: bool = False, refine=None, devices=None, want16: bool = False, census=None,
-                sgm=None) -> dict:
+                sgm=None, speckle=None) -> dict:
     """Frame API (``asw_create`` + ``asw_match``): host RGBA8 in, host maps out."""
     with FrameContext(params, devices=devices if devices is not None else (device,), refine=refine,
-                      census=census, sgm=sgm) as fc:
+                      census=census, sgm=sgm, speckle=speckle) as fc:
         return fc.match(left_rgba, right_rgba, want_cost=want_cost, want16=want16)
